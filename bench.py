@@ -1,20 +1,23 @@
 #!/usr/bin/env python
 """bench.py -- training samples/sec of the DeepCTR hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" = forward + BCE(sum) + backward (fused sparse embedding update) + dense optimizer step of DeepFM on
 one batch of 4096 synthetic Criteo-shaped samples (26 sparse x 1M-row vocab, 13 dense, emb_dim 16) whose
-dataset (4096 x 64 rows) is already resident in HBM.  Prints ONE JSON line (rank 0).  Besides the
-contract's keys it carries
+dataset (4096 x 64 rows) is already resident in HBM.  Prints ONE JSON line (rank 0).  A plain run does only what that
+line's headline needs: set up, warm up, time ONE block of exactly --steps steps (ms_per_step = its time / --steps), save the
+last step's outputs when --dump-outputs DIR is given, print.  With --full (the measurement set) the timed block is repeated
+(median of --repeats 5) and the line also carries
   roofline     the embedding update (the step's HBM-bound kernel): ALGORITHMIC bytes per launch / its
                duration INSIDE the step (HIP events on its queue); scalar keys beside it name the step's longest launch
                (dominant_kernel / _bound / _avg_us / _frac, timed inside hipGraph replays through dctr_stamp) and the clock
                and power the box held (sclk_mhz, power_w)
   cpu_baseline the UNMODIFIED reference (unpacked from oracle/_ref/, kind "reference"), timed on this box's host cores at
                the best thread count of a sweep, on a bounded sample (rank 0, N=1 only)
+  other_configs  xDeepFM, FiBiNET and further DeepFM legs under the same timed protocol (N=1 only)
 """
 import argparse
 import json
@@ -67,12 +70,22 @@ def parse():
                          "compared element by element) passes on EVERY rank, else rccl -- the JSON line and stderr say "
                          "which ran")
     ap.add_argument("--kernel-iters", type=int, default=50, help="event-timed launches per hot-path kernel")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed block of --steps steps is run this many times (each bracketed by a synchronize, and a "
-                         "barrier with N > 1); ms_per_step / value are the MEDIAN block, all blocks are listed")
-    ap.add_argument("--warmup-seconds", type=float, default=1.0,
+                         "barrier with N > 1); ms_per_step / value are the MEDIAN block, all blocks are listed.  Default: 1 "
+                         "(exactly --steps timed steps), 5 with --full")
+    ap.add_argument("--warmup-seconds", type=float, default=None,
                     help="besides --warmup steps: keep replaying until this much wall time has passed (clocks, caches and "
-                         "the allocator settle; a 20-step block is 2 ms of GPU time)")
+                         "the allocator settle; a 20-step block is 2 ms of GPU time).  Default: 1.0, but 0 with "
+                         "--dump-outputs (the number of steps trained before the dumped one must not depend on the speed)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel and in-graph timings, roofline, clock / power, the "
+                         "saturating launch, the other configurations (other_configs), the CPU baseline.  Off by default: a "
+                         "plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, save what the last timed step returned (loss, predictions) and the "
+                         "parameters it left (dense ones whole, the embedding tables as a fixed seeded sample of rows) "
+                         "as DIR/<name>.npy in float32")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the multi-process orchestration only (gloo instead of RCCL) -- there is NO CPU compute path: "
@@ -80,7 +93,12 @@ def parse():
     ap.add_argument("--diag-trace", default="",
                     help="development: load libdctr_hip_diag.so and save the tower kernels' per-workgroup phase stamps of "
                          "the last timed step (as replayed from the hipGraph) to this .npy file (tools/tower_trace.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.warmup_seconds is None:
+        args.warmup_seconds = 0.0 if args.dump_outputs else 1.0
+    return args
 
 
 def build_model(args, device):
@@ -739,7 +757,7 @@ def sharded_1rank(args):
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--force-parallel", "--exchange", "direct",
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-other-configs", "--no-cpu-baseline",
            "--batch", str(args.batch), "--vocab", str(args.vocab), "--optimizer", args.optimizer, "--kernel-iters", "2",
-           "--no-saturating"]
+           "--no-saturating", "--full"]
     env = dict(os.environ, MASTER_PORT=str(29600 + os.getpid() % 300), WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
@@ -871,6 +889,120 @@ def fit_api(args, device, X, y, epochs=5, tile=10):
     except Exception as exc:
         torch.cuda.synchronize()
         return {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
+
+
+def roofline_figures(args, model, X, y, B, ms, value, world, parallel, device):
+    """--full: the hot-path kernels timed on their own, inside eager steps and inside hipGraph replays, the clock / power the
+    box held, the PMC traffic and the saturating launch -- the `roofline` and `hot_path` objects of the result line.  Runs
+    train steps of its own: after the timed steps (and after --dump-outputs has saved them)."""
+    kern = time_hot_kernels(model, X, B, args.kernel_iters, args.optimizer)
+    alg = algorithmic_bytes(B, args.optimizer)
+    for k in kern:
+        kern[k]["alg_bytes"] = alg[k]
+        kern[k]["gbs"] = alg[k] / (kern[k]["avg_us"] * 1e-6) / 1e9
+    # the HBM-bound kernels compete for "dominant"; the id-only segment pre-pass (latency / LDS-bound, run in the
+    # tower's shadow) is listed with them in hot_path
+    dom = max((k for k in kern if k != "embed_segments"), key=lambda k: kern[k]["avg_us"])
+    # the step engine gathers inside the tower launch: the stand-alone gather kernel (still the lookup of every other
+    # model and of predict()) is timed above but is not a launch of this step
+    engine_on = parallel is None and model._fused_step_state() is not None and \
+        model._fused_step_state().get("engine") is not None
+    if engine_on:
+        kern["embed_fwd"]["in_step"] = False
+        dom = "embed_update"
+    in_step = time_update_in_step(model, X, y, B) if (engine_on and dom == "embed_update") else None
+    in_graph = time_kernels_in_graph(model, X, y, B) if engine_on else None
+    clk = gpu_clock_power(lambda: time_steps(model, X, y, B, 200, 1, args.steps_per_graph, not args.no_graph)[0]) \
+        if world == 1 else {}
+    traffic = pmc_traffic(dom, args.optimizer, B)
+    dom_us = in_step["avg_us"] if in_step else kern[dom]["avg_us"]
+    dom_gbs = alg[dom] / (dom_us * 1e-6) / 1e9
+    sat = saturating_launch(args, model, device) if (world == 1 and args.vocab >= 100000 and
+                                                     not args.no_saturating) else None
+    hot_us = sum(v["avg_us"] for v in kern.values())
+    step_alg = sum(alg[k] for k in kern)
+    # SURVEY.md 8(d)'s own per-sample figures: the whole train step (rows + ids + labels + dense parameters; Adagrad
+    # adds the state's read + write) and the update proper (row + state, read + write) -- next to the per-kernel count
+    # above, which also charges the re-read of the [B, ld] gradient strips, fm_s and the sorted keys
+    rows_b = F_SPARSE * DIM * 4 + F_SPARSE * 4                                   # 1768 B: one deep + one wide row per field
+    step_8d = (2 * rows_b + (F_SPARSE + N_DENSE) * 4 + 8 + 279) + (2 * rows_b if args.optimizer == "adagrad" else 0)
+    upd_8d = (4 if args.optimizer == "adagrad" else 2) * rows_b
+    # the tower launch (gather + tower forward + head + backward-data) is the step's LONGEST kernel and MFMA-bound:
+    # forward + backward-data = 2 x 2 x (429 x 256 + 256 x 128 + 128) flop per sample
+    k0 = F_SPARSE * DIM + N_DENSE
+    tower_flop = 2 * 2 * (k0 * 256 + 256 * 128 + 128) * B
+    tower = (in_step or {}).get("tower")
+    dominant = None
+    if tower:
+        tf = tower_flop / (tower["avg_us"] * 1e-6) / 1e12
+        dominant = {"kernel": "embed_tower_train", "bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS, "avg_us": tower["avg_us"],
+                    "flop_per_launch": tower_flop, "timed": "in step", "detail": tower,
+                    "note": "the step's longest launch (gather of the tile's rows + tower forward + head + BCE + "
+                            "backward-data); the HBM-bound kernel the roofline object describes is the second longest"}
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": dom_gbs / HBM_PEAK_GBS,
+                     "traffic": (traffic or {}).get("bytes"), "traffic_detail": traffic,
+                     "alg_bytes_per_launch": alg[dom], "avg_us": dom_us,
+                     "alg_bytes_per_sample": alg[dom] / B,
+                     "alg_bytes_per_sample_8d": upd_8d if dom == "embed_update" else None,
+                     "frac_8d": (upd_8d * B / (dom_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if dom == "embed_update" else None,
+                     "dominant": dominant,
+                     # scalar keys (a record that flattens nested objects keeps them): the step's LONGEST launch, timed
+                     # inside hipGraph replays (dctr_stamp launches around it: time_kernels_in_graph), the update the
+                     # same way, and the clock / power the box held while replaying train steps
+                     "dominant_kernel": "embed_tower_train" if in_graph else None,
+                     "dominant_bound": "mfma" if in_graph else None,
+                     "dominant_avg_us": (in_graph or {}).get("tower_us"),
+                     "dominant_frac": (tower_flop / (in_graph["tower_us"] * 1e-6) / 1e12 / MFMA_PEAK_TFLOPS)
+                     if (in_graph and in_graph.get("tower_us")) else None,
+                     "update_avg_us_in_graph": (in_graph or {}).get("update_us"),
+                     "update_frac_in_graph": (alg["embed_update"] / (in_graph["update_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS)
+                     if (in_graph and in_graph.get("update_us")) else None,
+                     "in_graph": in_graph,
+                     "sclk_mhz": clk.get("sclk_mhz"), "power_w": clk.get("power_w"),
+                     "whole_step_frac_8d": value / world * step_8d / 1e9 / HBM_PEAK_GBS,
+                     "whole_step_bytes_per_sample_8d": step_8d,
+                     "timed": "in step" if in_step else "stand-alone", "in_step": in_step,
+                     "standalone_avg_us": kern[dom]["avg_us"], "standalone_frac": kern[dom]["gbs"] / HBM_PEAK_GBS},
+        "hot_path": {"kernels": kern, "sum_us": hot_us, "saturating": sat,
+                     "frac_of_hbm_peak": step_alg / (hot_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                     "whole_step_frac_of_hbm_peak_kernel_bytes": step_alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                     "whole_step_frac_8d": value / world * step_8d / 1e9 / HBM_PEAK_GBS},
+    }
+
+
+DUMP_ROWS = 4096          # rows of every embedding table in a --dump-outputs sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, model=None):
+    """--dump-outputs: what the last timed step handed back -- its loss (BCE summed over the batch) and the batch's
+    predictions -- and, for a single-process model, the parameters it left behind: every dense parameter whole, every
+    embedding table as the same DUMP_ROWS rows drawn with a fixed seed (a 1M-row table is 64 MB on its own).  float32, one
+    DIR/<name>.npy per array."""
+    import numpy as np
+    arrays = {"loss": out[0], "predictions": out[-1]}
+    if model is not None:
+        rows = {}
+        for k, v in model.state_dict(keep_vars=True).items():
+            v = v.detach()
+            if v.dim() == 2 and v.shape[0] > DUMP_ROWS:
+                n = v.shape[0]
+                if n not in rows:
+                    gen = torch.Generator().manual_seed(n)
+                    rows[n] = torch.randperm(n, generator=gen)[:DUMP_ROWS].sort().values.to(v.device)
+                v = v.index_select(0, rows[n])
+            arrays["param." + k] = v
+    host = {k: v.detach().float().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print("bench: %d arrays (%.1f MB) -> %s" % (len(host), total / 1e6, path), file=sys.stderr, flush=True)
 
 
 def auto_steps_per_graph(steps):
@@ -1051,6 +1183,8 @@ def main():
     if trace_buf is not None:
         import numpy as np
         np.save(args.diag_trace, trace_buf.view(3, 4096, 16).cpu().numpy())
+    if args.dump_outputs and rank == 0:      # before anything else trains the model further
+        dump_outputs(args.dump_outputs, out, model if parallel is None else None)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -1064,51 +1198,6 @@ def main():
                 dist.barrier()
                 dist.destroy_process_group()
             return
-        kern = time_hot_kernels(model, X, B, args.kernel_iters, args.optimizer)
-        alg = algorithmic_bytes(B, args.optimizer)
-        for k in kern:
-            kern[k]["alg_bytes"] = alg[k]
-            kern[k]["gbs"] = alg[k] / (kern[k]["avg_us"] * 1e-6) / 1e9
-        # the HBM-bound kernels compete for "dominant"; the id-only segment pre-pass (latency / LDS-bound, run in the
-        # tower's shadow) is listed with them in hot_path
-        dom = max((k for k in kern if k != "embed_segments"), key=lambda k: kern[k]["avg_us"])
-        # the step engine gathers inside the tower launch: the stand-alone gather kernel (still the lookup of every other
-        # model and of predict()) is timed above but is not a launch of this step
-        engine_on = parallel is None and model._fused_step_state() is not None and \
-            model._fused_step_state().get("engine") is not None
-        if engine_on:
-            kern["embed_fwd"]["in_step"] = False
-            dom = "embed_update"
-        in_step = time_update_in_step(model, X, y, B) if (engine_on and dom == "embed_update") else None
-        in_graph = time_kernels_in_graph(model, X, y, B) if engine_on else None
-        clk = gpu_clock_power(lambda: time_steps(model, X, y, B, 200, 1, args.steps_per_graph, not args.no_graph)[0]) \
-            if (world == 1 and on_gpu) else {}
-        traffic = pmc_traffic(dom, args.optimizer, B)
-        dom_us = in_step["avg_us"] if in_step else kern[dom]["avg_us"]
-        dom_gbs = alg[dom] / (dom_us * 1e-6) / 1e9
-        sat = saturating_launch(args, model, device) if (world == 1 and args.vocab >= 100000 and
-                                                         not args.no_saturating) else None
-        hot_us = sum(v["avg_us"] for v in kern.values())
-        step_alg = sum(alg[k] for k in kern)
-        # SURVEY.md 8(d)'s own per-sample figures: the whole train step (rows + ids + labels + dense parameters; Adagrad
-        # adds the state's read + write) and the update proper (row + state, read + write) -- next to the per-kernel count
-        # above, which also charges the re-read of the [B, ld] gradient strips, fm_s and the sorted keys
-        rows_b = F_SPARSE * DIM * 4 + F_SPARSE * 4                                   # 1768 B: one deep + one wide row per field
-        step_8d = (2 * rows_b + (F_SPARSE + N_DENSE) * 4 + 8 + 279) + (2 * rows_b if args.optimizer == "adagrad" else 0)
-        upd_8d = (4 if args.optimizer == "adagrad" else 2) * rows_b
-        # the tower launch (gather + tower forward + head + backward-data) is the step's LONGEST kernel and MFMA-bound:
-        # forward + backward-data = 2 x 2 x (429 x 256 + 256 x 128 + 128) flop per sample
-        k0 = F_SPARSE * DIM + N_DENSE
-        tower_flop = 2 * 2 * (k0 * 256 + 256 * 128 + 128) * B
-        tower = (in_step or {}).get("tower")
-        dominant = None
-        if tower:
-            tf = tower_flop / (tower["avg_us"] * 1e-6) / 1e12
-            dominant = {"kernel": "embed_tower_train", "bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS,
-                        "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS, "avg_us": tower["avg_us"],
-                        "flop_per_launch": tower_flop, "timed": "in step", "detail": tower,
-                        "note": "the step's longest launch (gather of the tile's rows + tower forward + head + BCE + "
-                                "backward-data); the HBM-bound kernel the roofline object describes is the second longest"}
         result = {
             "metric": "training samples/sec DeepFM Criteo batch=4096", "value": value, "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -1121,40 +1210,13 @@ def main():
                        "eager_steps_in_timed_region": 0 if graphed else args.steps,
                        "warmup_steps_run": did_warm, "optimizer": args.optimizer,
                        "exchange": exch_info if parallel is not None else None},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": dom_gbs / HBM_PEAK_GBS,
-                         "traffic": (traffic or {}).get("bytes"), "traffic_detail": traffic,
-                         "alg_bytes_per_launch": alg[dom], "avg_us": dom_us,
-                         "alg_bytes_per_sample": alg[dom] / B,
-                         "alg_bytes_per_sample_8d": upd_8d if dom == "embed_update" else None,
-                         "frac_8d": (upd_8d * B / (dom_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if dom == "embed_update" else None,
-                         "dominant": dominant,
-                         # scalar keys (a record that flattens nested objects keeps them): the step's LONGEST launch, timed
-                         # inside hipGraph replays (dctr_stamp launches around it: time_kernels_in_graph), the update the
-                         # same way, and the clock / power the box held while replaying train steps
-                         "dominant_kernel": "embed_tower_train" if in_graph else None,
-                         "dominant_bound": "mfma" if in_graph else None,
-                         "dominant_avg_us": (in_graph or {}).get("tower_us"),
-                         "dominant_frac": (tower_flop / (in_graph["tower_us"] * 1e-6) / 1e12 / MFMA_PEAK_TFLOPS)
-                         if (in_graph and in_graph.get("tower_us")) else None,
-                         "update_avg_us_in_graph": (in_graph or {}).get("update_us"),
-                         "update_frac_in_graph": (alg["embed_update"] / (in_graph["update_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS)
-                         if (in_graph and in_graph.get("update_us")) else None,
-                         "in_graph": in_graph,
-                         "sclk_mhz": clk.get("sclk_mhz"), "power_w": clk.get("power_w"),
-                         "whole_step_frac_8d": value / world * step_8d / 1e9 / HBM_PEAK_GBS,
-                         "whole_step_bytes_per_sample_8d": step_8d,
-                         "timed": "in step" if in_step else "stand-alone", "in_step": in_step,
-                         "standalone_avg_us": kern[dom]["avg_us"], "standalone_frac": kern[dom]["gbs"] / HBM_PEAK_GBS},
-            "hot_path": {"kernels": kern, "sum_us": hot_us, "saturating": sat,
-                         "frac_of_hbm_peak": step_alg / (hot_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                         "whole_step_frac_of_hbm_peak_kernel_bytes": step_alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "whole_step_frac_8d": value / world * step_8d / 1e9 / HBM_PEAK_GBS},
-            "final_loss": last_loss,
-            "timing": dict(spread(times, args.steps), warmup_seconds=args.warmup_seconds,
-                           protocol="value / ms_per_step = the median of `blocks` timed blocks of exactly `steps` steps"),
         }
-        if world == 1 and not args.no_other_configs:
+        if args.full:
+            result.update(roofline_figures(args, model, X, y, B, ms, value, world, parallel, device))
+        result["final_loss"] = last_loss
+        result["timing"] = dict(spread(times, args.steps), warmup_seconds=args.warmup_seconds,
+                                protocol="value / ms_per_step = the median of `blocks` timed blocks of exactly `steps` steps")
+        if args.full and world == 1 and not args.no_other_configs:
             del model
             torch.cuda.empty_cache()
             want = (lambda t: True) if args.legs == "all" else (lambda t: t in args.legs.split(","))
@@ -1178,7 +1240,7 @@ def main():
             if "value" in fa:
                 fa["vs_step_runner"] = fa["value"] / value
                 fa["shuffle_false"]["vs_step_runner"] = fa["shuffle_false"]["value"] / value
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args)
     if dist:
         dist.barrier()

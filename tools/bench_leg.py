@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 leg = sys.argv[1]
-sys.argv = [sys.argv[0]] + sys.argv[2:]
+sys.argv = [sys.argv[0], "--full"] + sys.argv[2:]      # the legs' protocol of other_configs: median of 5 blocks
 import bench  # noqa: E402
 
 args = bench.parse()

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/bench_head
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline "$@" > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline "$@" > $O/bench.json 2> $O/bench.err
 tail -3 $O/bench.err
 python - <<PY
 import json

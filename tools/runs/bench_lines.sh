@@ -2,8 +2,8 @@
 # the two bench lines kept under profiles/: the driver's flags and the default flags
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT; O=gpurun_out
-( timeout 600 python bench.py --steps 20 --warmup 5 ) 2> $O/bench_driver_flags.err | grep '^{' > $O/bench_driver_flags.json
-( timeout 900 python bench.py ) 2> $O/bench.err | grep '^{' > $O/bench.json
+( timeout 600 python bench.py --full --steps 20 --warmup 5 ) 2> $O/bench_driver_flags.err | grep '^{' > $O/bench_driver_flags.json
+( timeout 900 python bench.py --full ) 2> $O/bench.err | grep '^{' > $O/bench.json
 python - <<PY
 import json
 for f in ("bench_driver_flags", "bench"):

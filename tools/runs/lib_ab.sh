@@ -11,7 +11,7 @@ cp $L /tmp/ship.so
 for rep in $(seq 1 $R); do
   for v in ship variant; do
     if [ $v = ship ]; then cp /tmp/ship.so $L; else cp $V $L; fi
-    timeout 600 python bench.py --gpus 1 --steps 100 --warmup 10 --no-other-configs --no-cpu-baseline "$@" > $O/head_${v}_$rep.json 2> $O/head_${v}_$rep.err
+    timeout 600 python bench.py --full --gpus 1 --steps 100 --warmup 10 --no-other-configs --no-cpu-baseline "$@" > $O/head_${v}_$rep.json 2> $O/head_${v}_$rep.err
     python - <<PY | tee -a $O/summary.txt
 import json
 try:

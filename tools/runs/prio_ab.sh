@@ -11,7 +11,7 @@ for rep in 1 2; do
   for v in prio noprio; do
     if [ $v = prio ]; then cp /tmp/prio.so $L; else cp gpurun_in_noprio.so $L; fi
     DCTR_LAZY_SWEEP_WAVES=0 timeout 600 python tools/bench_leg.py default_kwargs --steps 20 --warmup 5 > $O/leg_${v}_$rep.json 2> $O/leg_${v}_$rep.err
-    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/head_${v}_$rep.json 2> $O/head_${v}_$rep.err
+    timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/head_${v}_$rep.json 2> $O/head_${v}_$rep.err
     python - <<PY | tee -a $O/summary.txt
 import json
 def last(p):

@@ -5,7 +5,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/sharded
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0
-timeout 300 python bench.py --gpus 1 --force-parallel --exchange direct --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --gpus 1 --force-parallel --exchange direct --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 try:
@@ -13,7 +13,7 @@ try:
 except Exception as e: print("failed", e); print(open("$O/bench.err").read()[-1500:])
 PY
 rm -rf $O/trace
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o t -- python bench.py --gpus 1 --force-parallel --exchange direct --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 --warmup-seconds 0.2 --repeats 1 > $O/trace.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o t -- python bench.py --full --gpus 1 --force-parallel --exchange direct --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 --warmup-seconds 0.2 --repeats 1 > $O/trace.log 2>&1
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python - "$f" > $O/timeline.txt <<'PY'
 import csv, re, sys
@@ -38,7 +38,7 @@ PY
 cat $O/timeline.txt | head -90
 rm -rf $O/trace
 for st in 100 200; do
-timeout 300 python bench.py --gpus 1 --force-parallel --exchange direct --steps $st --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 > $O/bench_$st.json 2> $O/bench_$st.err
+timeout 300 python bench.py --full --gpus 1 --force-parallel --exchange direct --steps $st --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --kernel-iters 2 > $O/bench_$st.json 2> $O/bench_$st.err
 python - <<PY
 import json
 try:

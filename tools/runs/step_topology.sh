@@ -13,7 +13,7 @@ tests)
   tail -12 $O/pytest.txt ;;
 bench)
   for topo in weights_flag update_side; do
-    DCTR_STEP_TOPOLOGY=$topo timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating > $O/bench_$topo.json 2> $O/bench_$topo.err
+    DCTR_STEP_TOPOLOGY=$topo timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating > $O/bench_$topo.json 2> $O/bench_$topo.err
     python - <<PY
 import json
 try:
@@ -25,7 +25,7 @@ PY
   done ;;
 trace)
   rm -rf $O/trace
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --warmup-seconds 0.2 --repeats 1 > $O/trace.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-saturating --warmup-seconds 0.2 --repeats 1 > $O/trace.log 2>&1
   f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
   cp $f $O/kernel_trace.csv
   python tools/timeline.py $f 24 90 > $O/timeline.txt 2>&1

@@ -15,7 +15,7 @@ try:
 except Exception as e: print("waves $w failed", e); print(open("$O/leg_$w.err").read()[-800:])
 PY
 done
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/headline.json 2> $O/headline.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/headline.json 2> $O/headline.err
 python - <<PY | tee -a $O/summary.txt
 import json
 try:
