@@ -61,32 +61,20 @@ class DenseSlab(object):
         self._fork = None
         self._pending = None
         self.deferred = None      # overlap == "defer": the closure that enqueues the weight-gradient kernels
-        self.after_update = None  # topology "tower_side": enqueues the forked weight gradients behind the update's launch
         # in-kernel optimizer step (single-GPU fused train step): the kernels that finish the dense gradients (the
         # tower's weight-gradient reduction, the update kernel's Linear.weight workgroups) also step the parameters,
         # and the embedding update runs on a side stream beside them -- see begin_inline_step()
         self.inline = None        # DenseStep while a fused train step with in-kernel optimizer is being assembled
         self.inline_done = False  # the kernels of this step applied it: step() has nothing left to do
-        self.wgrad_side = False   # topology of the in-kernel-optimizer step: True = weight gradients on the fork stream
-        self.wgrad_on_seg = False  # ... and that fork stream is the pre-pass's ("tower_seg")
-        self.flag_sync = False    # topology "flags": gather_side with the two cross-queue edges replaced by dctr_step_wait
-        self.sync_timeout_us = 20000
-        self._sync = None         # the sync block (int32[16], zero at rest between steps' signal / wait pairs)
-        self.upd_keep = None      # tower_seg: the operands of the last embedding update (alive until the next one is enqueued)
-        self.gather_side = False  # ... True = gather AND update on the pre-pass's stream (ops.EmbedFunction.forward)
-        self.main_keep = None     # gather_side: tensors the main stream's weight-gradient kernels of the last step read
         self.update_stream = None  # the side stream of this step's segment pre-pass (set by ops.EmbedFunction.forward):
         #                            the tower + head launch makes it wait for itself, the update then runs there
 
     def __getstate__(self):
         d = dict(self.__dict__)
         d["_lay"] = [self._lay[id(p)] for p in self.params]     # id() keys do not survive pickling
-        d["_fork"] = d["_pending"] = d["deferred"] = d["after_update"] = None   # streams / events / closures: per process
+        d["_fork"] = d["_pending"] = d["deferred"] = None   # streams / closures: per process
         d["overlap"] = False
-        d["inline"] = d["update_stream"] = d["main_keep"] = d["upd_keep"] = d["_sync"] = None
-        d["flag_sync"] = False
-        d["wgrad_side"] = d["gather_side"] = d["wgrad_on_seg"] = False
-        d["_fork_events"] = None
+        d["inline"] = d["update_stream"] = None
         d["inline_done"] = False
         return d
 
@@ -122,8 +110,8 @@ class DenseSlab(object):
         self.inline = None
         self.update_stream = None
 
-    def fork_stream(self, device, force=False):
-        if not force and (not self.overlap or self.overlap == "defer" or torch.device(device).type != "cuda"):
+    def fork_stream(self, device):
+        if not self.overlap or self.overlap == "defer" or torch.device(device).type != "cuda":
             return None
         if self._pending is not None:
             self.join()
@@ -131,62 +119,14 @@ class DenseSlab(object):
             self._fork = _streams.side_stream(device, "fork")
         return self._fork
 
-    def side_chain_open(self, side):
-        """True when ``side`` still carries the previous step's un-joined update and is part of the running hipGraph
-        capture: work enqueued on it now is ordered behind that update without waiting for the current stream."""
-        p = self._pending
-        if p is None or side is None or p[0] is not side or not torch.cuda.is_current_stream_capturing():
-            return False
-        with torch.cuda.stream(side):
-            return bool(torch.cuda.is_current_stream_capturing())
-
-    def sync_block(self, device):
-        """The step's device-side dependency words (include/dctr.h: dctr_step_wait).  Allocated once, outside any
-        hipGraph capture's pool."""
-        if self._sync is None or self._sync.device != torch.device(device):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("the step's sync block must exist before a hipGraph capture begins (run one eager step)")
-            self._sync = torch.zeros(L.SYNC_INTS, dtype=torch.int32, device=device)
-        return self._sync
-
-    def check_sync(self, reset=False):
-        """Raise if a dctr_step_wait ever timed out (synchronises the device).  ``reset``: zero the block -- after an
-        exception interrupted a step between a signal and its wait."""
-        if self._sync is None:
-            return
-        torch.cuda.synchronize(self._sync.device)
-        bad = int(self._sync[L.SYNC_ERR].item())
-        if reset or bad:
-            self._sync.zero_()
-            torch.cuda.synchronize(self._sync.device)
-        if bad:
-            raise RuntimeError("a device-side step dependency timed out (signals %s): kernels of the two queues were not "
-                               "running concurrently (a profiler serialising kernels?) -- results since then are invalid; "
-                               "set DCTR_STEP_TOPOLOGY=update_side" % bin(bad))
-
-    def fork_event(self, k):
-        """Two events that live as long as the slab (an event created inside a hipGraph capture and collected during a
-        later one aborts the process: graph.no_gc_during_capture)."""
-        ev = getattr(self, "_fork_events", None)
-        if ev is None:
-            ev = self._fork_events = [torch.cuda.Event(), torch.cuda.Event()]
-        return ev[k]
-
-    def forked(self, stream, keep_alive, done=None):
-        """``done``: an event recorded behind the forked work -- join() then waits for IT instead of the stream's tail
-        (the stream goes on to carry work the joiner must not wait for)."""
-        self._pending = (stream, keep_alive, done)
+    def forked(self, stream, keep_alive):
+        self._pending = (stream, keep_alive)
 
     def join(self):
         p = self._pending
-        self.main_keep = None
         if p is not None:
             self._pending = None
-            cur = torch.cuda.current_stream(self.flat.device)
-            if len(p) > 2 and p[2] is not None:
-                cur.wait_event(p[2])
-            else:
-                cur.wait_stream(p[0])
+            torch.cuda.current_stream(self.flat.device).wait_stream(p[0])
         # (the tensors of keep_alive are released only now, on the stream that has just waited for their last reader)
 
     def __setstate__(self, d):

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -31,7 +31,7 @@ class Plan(ctypes.Structure):
                 ("n_dense", ctypes.c_int32), ("n_wdense", ctypes.c_int32), ("dense_off", ctypes.c_int32),
                 ("emb_dim", ctypes.c_int32), ("n_xcols", ctypes.c_int32), ("n_wide_fixed", ctypes.c_int32),
                 ("max_dim", ctypes.c_int32), ("vec", ctypes.c_int32), ("flags", ctypes.c_int32),
-                ("step_sync", ctypes.c_void_p), ("out_chunks", ctypes.c_void_p), ("chunk_rows", ctypes.c_int32),
+                ("out_chunks", ctypes.c_void_p), ("chunk_rows", ctypes.c_int32),
                 ("pad_", ctypes.c_int32), ("ext", ctypes.c_void_p)]
 
 
@@ -76,7 +76,7 @@ class MlpLayer(ctypes.Structure):
 class Mlp(ctypes.Structure):
     """``dctr_mlp_t`` (include/dctr.h) -- host struct, device pointers."""
     _fields_ = [("layer", MlpLayer * MLP_MAX_LAYERS), ("w_out", ctypes.c_void_p), ("g_w_out", ctypes.c_void_p),
-                ("n_layers", ctypes.c_int32), ("pad_", ctypes.c_int32), ("step_sync", ctypes.c_void_p)]
+                ("n_layers", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 class DenseStep(ctypes.Structure):
@@ -92,7 +92,6 @@ class DenseItem(ctypes.Structure):
 
 
 PLAN_HAS_GACC, PLAN_HAS_STATE, PLAN_HAS_MAXPOOL = 1, 2, 4
-SYNC_TOWER, SYNC_GATHER, SYNC_UPDATE, SYNC_ERR, SYNC_INTS = 0, 1, 2, 12, 32
 LAZY_SGD, LAZY_ADAGRAD, LAZY_ADAM, LAZY_RMSPROP = 0, 1, 2, 3
 
 
@@ -202,13 +201,7 @@ SIGNATURES = {
     "dctr_embed_tower_train_supported": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.POINTER(Mlp), _I32]),
     "dctr_embed_tower_train_step": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I64, ctypes.POINTER(Mlp), _I32, _I32, _P, _P,
                                                    _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
-    "dctr_mlp_train_wgrad_counters": (ctypes.c_size_t, [ctypes.POINTER(Mlp), _I32]),
-    "dctr_mlp_train_wgrad_sync": (ctypes.c_int, [ctypes.POINTER(Mlp), _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "dctr_embed_tower_train_step_sync": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I64, ctypes.POINTER(Mlp), _I32, _I32, _P,
-                                                        _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I32, _P]),
     "dctr_sizeof_dense_step": (ctypes.c_size_t, []),
-    "dctr_step_wait": (ctypes.c_int, [_P, _I32, _I32, _P]),
-    "dctr_step_signal": (ctypes.c_int, [_P, _I32, _P]),
     "dctr_stamp": (ctypes.c_int, [_P, _P]),
     "dctr_copy_async": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),
     "dctr_enable_peer_access": (ctypes.c_int, [_I32]),

@@ -537,87 +537,32 @@ class TowerHeadFunction(torch.autograd.Function):
         _fill(desc, meta, Ws, lds, bp, hs, dhs, gWs, gbs, wo, g_wo)
         ws = torch.empty((max(1, lib.dctr_mlp_train_workspace_floats(ctypes.byref(desc), B)),), dtype=torch.float32,
                          device=dev)
-        # topology "flags": the tower + head launch signals gx / g_logit complete in the step's sync block and the
-        # update's stream waits for THAT (dctr_step_wait) instead of an event of this stream
-        sync = None
-        if getattr(sink, "flag_sync", False) and getattr(sink, "inline", None) is not None and \
-                getattr(sink, "update_stream", None) is not None and x.device.type == "cuda":
-            sync = sink.sync_block(dev)
-            desc.step_sync = sync.data_ptr()
         pp = [_ptr(p) for p in ps] + [None] * (2 - len(ps))
         # The weight gradients need only what the first launch leaves behind (x, h, dh, g_logit) and nothing but the
         # dense optimizer needs THEM: with a fork stream on the sink they run beside the embedding update (which needs
         # only gx / g_logit) instead of in front of it.  The sink joins the fork before the dense optimizer step.
         inline = getattr(sink, "inline", None)
-        if inline is not None and hasattr(sink, "join") and not getattr(sink, "gather_side", False):
+        if inline is not None and hasattr(sink, "join"):
             sink.join()       # a previous step's forked weight-gradient / optimizer kernels wrote the weights read below
-        # (gather_side: the fork holds the embedding update and this step's gather -- the tower reads nothing they
-        # write but the gathered rows, for which the gather's own launch made this stream wait)
         fork = sink.fork_stream(dev) if (hasattr(sink, "fork_stream") and inline is None) else None
         defer = fork is None and inline is None and getattr(sink, "overlap", False) == "defer" and x.device.type == "cuda"
         L.check(lib.dctr_mlp_train_step(ctypes.byref(desc), _ptr(x), x.stride(0), B, pp[0], pp[1], _ptr(bias), _ptr(y),
                                         _ptr(y_pred), _ptr(loss), _ptr(g_logit), _ptr(g_bias), _ptr(gx), gx.stride(0),
                                         _ptr(ws), 1 if (fork is not None or defer or inline is not None) else 0, None,
                                         L.stream_handle(dev)), "dctr_mlp_train_step")
-        if inline is not None and getattr(sink, "wgrad_side", False) and x.device.type == "cuda":
-            # Topology "tower_side": the weight gradients + their reduction (which also steps the parameters) go to
-            # the fork stream, the embedding update stays on this one; nothing joins them until the NEXT tower launch
-            # needs the stepped weights (DenseSlab.join() at the top of this function's next call, or at the end of the
-            # step when the caller may read parameters).  Main chain: gather, tower, update, next gather.
-            # The fork is ENQUEUED only after the embedding update has been (ops.EmbedFunction.backward calls
-            # `sink.after_update`): hipGraph keeps a node's FIRST child on the node's own queue and sends later children
-            # to other queues, whatever stream they were captured on -- launched here, ahead of the update, the weight
-            # gradients stayed on the tower's queue and the update (the longer chain since round 3) paid a cross-queue
-            # edge on both ends (~10 us each).
-            # "tower_seg" (round 3): the fork IS the pre-pass's stream -- two queues in all (main: gather, tower, update;
-            # side: ids, pre-pass, weight gradients + reduction), and the next tower launch waits for an event recorded
-            # right behind the reduction, not for the side stream's tail (by then the next step's pre-pass).
-            # tools/micro/topobench.hip (kernels that only busy-wait their body times) gives this recipe a period 4 us
-            # shorter than "update_side".  The real step is SLOWER (0.107 ms against 0.097, profiles/
-            # r03_step_topologies.json): the update and the weight gradients now start within a microsecond of each other
-            # and k_mlp_wgrad takes 38-40 us beside the update's 1118 workgroups (22 us with the 6 us head start it has
-            # in "update_side"), and that kernel is on this recipe's critical cycle.  Kept as an option, not the default.
-            seg = getattr(sink, "update_stream", None) if getattr(sink, "wgrad_on_seg", False) else None
-            side = seg if seg is not None else sink.fork_stream(dev, force=True)
-            ev = sink.fork_event(0)
-            ev.record(torch.cuda.current_stream(dev))       # fork point: right behind the tower kernel
-            keep = (x, hs, dhs, ws, g_logit, loss, ps, y, wo, desc, inline)
-
-            def launch_fork(side=side, ev=ev, keep=keep, B=B, g_bias=g_bias, by_event=seg is not None):
-                x_, ws_, g_logit_, loss_, desc_, inline_ = keep[0], keep[3], keep[4], keep[5], keep[9], keep[10]
-                side.wait_event(ev)
-                L.check(lib.dctr_mlp_train_wgrad(ctypes.byref(desc_), _ptr(x_), x_.stride(0), B, _ptr(g_logit_),
-                                                 _ptr(ws_), _ptr(loss_), _ptr(g_bias), ctypes.byref(inline_),
-                                                 ctypes.c_void_p(side.cuda_stream)), "dctr_mlp_train_wgrad")
-                done = None
-                if by_event:
-                    done = sink.fork_event(1)
-                    done.record(side)
-                sink.forked(side, keep, done)
-            sink.after_update = launch_fork
-            sink.inline_done = True
-            sink.update_stream = None            # (the update runs on this stream: ops.EmbedFunction.backward)
-        elif inline is not None:
+        if inline is not None:
             # In-kernel optimizer: the weight gradients and their reduction follow in line on THIS stream and step the
             # parameters as they finish; the embedding update (which needs only gx / g_logit) is what leaves for the
             # side stream (ops.EmbedFunction.backward), right behind the event recorded here.  The step's critical
             # chain -- gather, tower, weight gradients -- then never crosses a queue (a cross-queue dependency costs
             # 6-10 us on this stack; round 1 paid two per step).
             upd = getattr(sink, "update_stream", None)
-            if upd is not None and sync is not None:
-                L.check(lib.dctr_step_wait(_ptr(sync), L.SYNC_TOWER, sink.sync_timeout_us,
-                                           ctypes.c_void_p(upd.cuda_stream)), "dctr_step_wait(tower)")
-            elif upd is not None:
+            if upd is not None:
                 upd.wait_stream(torch.cuda.current_stream(dev))      # the update may start once this launch is done
             L.check(lib.dctr_mlp_train_wgrad(ctypes.byref(desc), _ptr(x), x.stride(0), B, _ptr(g_logit), _ptr(ws),
                                              _ptr(loss), _ptr(g_bias), ctypes.byref(inline), L.stream_handle(dev)),
                     "dctr_mlp_train_wgrad")
             sink.inline_done = True
-            if getattr(sink, "gather_side", False):
-                # What the weight-gradient kernels above read stays allocated until the NEXT tower launch: the next
-                # step's gather runs on the side stream, ordered behind this launch's first kernel only -- memory the
-                # allocator handed from these tensors to the gather's outputs would be overwritten under the reader.
-                sink.main_keep = (x, hs, dhs, ws, g_logit, loss, ps, y, wo, gx)
         if defer:
             keep = (x, hs, dhs, ws, g_logit, loss, ps, y, wo, gx, desc)
 

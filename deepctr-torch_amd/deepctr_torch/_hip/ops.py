@@ -94,60 +94,21 @@ class EmbedFunction(torch.autograd.Function):
         ctx.seg_event = None
         err = plan.err_flag(X.device)
 
-        def gather(stream, with_ids, signal=None):
-            # signal: the step's sync block (dense.DenseSlab.sync_block) -- the gather stores its outputs write-through
-            # and signals DCTR_SYNC_GATHER; the tower's stream waits for that with dctr_step_wait, not for an event
-            plan.cplan.step_sync = signal.data_ptr() if signal is not None else None
+        def gather(stream, with_ids):
             fused_ids = with_ids and plan.gen is None      # (a general unit spans several X columns: dctr_embed_ids)
-            try:
-                L.check(lib.dctr_embed_fwd(cplan, _ptr(X), X.stride(0), B, _ptr(out), plan.ld_out, _ptr(wide), 1,
-                                           _ptr(fm), _ptr(err), plan.units_ptr(), plan.n_grid_units,
-                                           _ptr(ids_t) if fused_ids else None, _ptr(parts_t) if fused_ids else None,
-                                           _ptr(fm_s), ld_s, stream), "dctr_embed_fwd")
-            finally:
-                plan.cplan.step_sync = None
+            L.check(lib.dctr_embed_fwd(cplan, _ptr(X), X.stride(0), B, _ptr(out), plan.ld_out, _ptr(wide), 1,
+                                       _ptr(fm), _ptr(err), plan.units_ptr(), plan.n_grid_units,
+                                       _ptr(ids_t) if fused_ids else None, _ptr(parts_t) if fused_ids else None,
+                                       _ptr(fm_s), ld_s, stream), "dctr_embed_fwd")
             if with_ids and not fused_ids and ids_t is not None:
                 L.check(lib.dctr_embed_ids(cplan, plan.units_ptr(), plan.n_grid_units, _ptr(X), X.stride(0), B,
                                            _ptr(ids_t), _ptr(parts_t), stream), "dctr_embed_ids")
 
-        if own_ids and getattr(sink, "gather_side", False):
-            # Topology "gather_side": the gather runs on the side stream too, in stream order behind the previous
-            # step's update (the only thing it depends on), so the next step's rows are being fetched while the main
-            # stream still finishes this step's weight gradients; the main stream waits for the gather alone.  Inside
-            # a multi-step capture the side stream does not wait for the main one first (that would be the previous
-            # step's weight-gradient reduction): it does only when it has to -- first step of a capture, eager steps
-            # (whatever produced X ran on the main stream), tables last written elsewhere.
-            sync = sink.sync_block(X.device) if getattr(sink, "flag_sync", False) else None
-            ctx.seg_event = plan.launch_segments(ids_t, parts_t, B, before=lambda st: gather(st, True, sync),
-                                                 fork=not sink.side_chain_open(plan._seg_stream),
-                                                 join_before=sync is None)
-            if ctx.seg_event[0] is not True:
-                sink.update_stream = ctx.seg_event[0]
-            if sync is not None:
-                # Topology "flags": no graph edge between the two queues inside a step.  A one-wave kernel on THIS
-                # stream waits for the gather's signal (4.6 us from the gather's last workgroup to the tower's first,
-                # against 11-12 us through a cross-queue hipGraph edge: tools/micro/hopbench.hip)
-                L.check(lib.dctr_step_wait(_ptr(sync), L.SYNC_GATHER, sink.sync_timeout_us,
-                                           L.stream_handle(X.device)), "dctr_step_wait(gather)")
-        else:
-            if own_ids and getattr(sink, "wgrad_on_seg", False):
-                # Topology "tower_seg": the side stream carries ids, pre-pass and (behind the tower) the weight gradients +
-                # their reduction; the update runs on the MAIN stream.  Inside a multi-step capture the pre-pass does not
-                # wait for the main stream (= for the previous step's update): with that edge hipGraph puts the weight
-                # gradients on the gather's queue and serialises the step (tools/micro/topobench.hip, recipe V1b:
-                # 127 us against 93).  What the edge protected is kept apart instead: the bucket workspace alternates
-                # between two tensors, and the previous update's operands stay allocated until this step's update has
-                # been enqueued (sink.upd_keep), so nothing the side stream writes now can be memory they still read.
-                plan._ws_slot = 1 - getattr(plan, "_ws_slot", 1)
-                ctx.seg_event = plan.launch_segments(ids_t, parts_t, B, X=X, slot=plan._ws_slot,
-                                                     fork=not sink.side_chain_open(plan._seg_stream))
-                if ctx.seg_event[0] is not True:
-                    sink.update_stream = ctx.seg_event[0]
-            elif own_ids:
-                ctx.seg_event = plan.launch_segments(ids_t, parts_t, B, X=X)
-                if ctx.seg_event[0] is not True:              # (True: the CPU stand-in, no streams)
-                    sink.update_stream = ctx.seg_event[0]     # where this step's update will run (see backward)
-            gather(L.stream_handle(X.device), not own_ids)
+        if own_ids:
+            ctx.seg_event = plan.launch_segments(ids_t, parts_t, B, X=X)
+            if ctx.seg_event[0] is not True:              # (True: the CPU stand-in, no streams)
+                sink.update_stream = ctx.seg_event[0]     # where this step's update will run (see backward)
+        gather(L.stream_handle(X.device), not own_ids)
         ctx.plan, ctx.want_fm = plan, want_fm
         if segs and not own_ids:
             ctx.seg_event = plan.launch_segments(ids_t, parts_t, B)
@@ -261,12 +222,6 @@ class EmbedFunction(torch.autograd.Function):
             if side is not None:
                 # (everything the side-stream kernels touch stays allocated until the join)
                 sink.forked(side, (X, out, ids_t, parts_t, fm_s, g_out, g_fm, g_wide, g_wd, ws, den_t, amax))
-            elif sink is not None and getattr(sink, "wgrad_on_seg", False):
-                sink.upd_keep = (X, out, ids_t, parts_t, fm_s, g_out, g_fm, g_wide, g_wd, ws, den_t, amax)   # (see forward)
-            after = getattr(sink, "after_update", None) if sink is not None else None
-            if after is not None:        # topology "tower_side": the weight gradients fork off behind the update's launch
-                sink.after_update = None
-                after()
             return None, None, None, g_w, None, None
 
         # general path (pooled VarLen fields, shared tables, very large batches): atomic scatter (+ consume pass)

@@ -530,7 +530,7 @@ class EmbeddingPlan(object):
         return den, am
 
     def point_step_buffers(self, den_t, amax):
-        """Aim the ext block at this step's side buffers (read at enqueue time, like dctr_plan_t.step_sync)."""
+        """Aim the ext block at this step's side buffers (read at enqueue time)."""
         self._step_bufs = (den_t, amax)         # (bind() re-creates the ext block when a table pointer moved)
         if self.gen is not None and self.cext is not None:
             self.cext.den_t = den_t.data_ptr() if den_t is not None else None
@@ -649,20 +649,7 @@ class EmbeddingPlan(object):
             bits = int(self._err.item())
             if bits != 0:
                 self._err.zero_()
-                import os
-                if (bits & 12) and os.environ.get("DCTR_DBG_IGNORE_WAIT") == "1":       # (timing experiments only)
-                    import sys
-                    print("dctr: an in-kernel wait timed out (bits %d) -- ignored (DCTR_DBG_IGNORE_WAIT)" % bits, file=sys.stderr)
-                    return
-                if bits & 12:   # (dctr_embed_tower_train_step_sync: its wait for the weights' generation ran out)
-                    raise RuntimeError("a train step's tower launch gave up waiting for the previous step's dense optimizer "
-                                       "step (DCTR_SYNC_W_GEN): the two queues of the step fell out of step -- results "
-                                       "since the last check are not to be trusted (DCTR_STEP_TOPOLOGY=update_side avoids "
-                                       "the in-kernel wait)")
                 raise IndexError("index out of range in self: a sparse id in X is outside [0, vocabulary_size)")
-        owner = getattr(self, "_sync_owner", None)      # step topology "flags": did a device-side dependency time out?
-        if owner is not None:
-            owner.check_sync()
 
     def dense_matrix(self, X, cols):
         lo, hi = cols[0], cols[-1] + 1
@@ -792,7 +779,7 @@ class EmbeddingPlan(object):
     def units_ptr(self):
         return ctypes.c_void_p(self._dev["units"].data_ptr())
 
-    def update_workspace(self, B, device, always=False, slot=0):
+    def update_workspace(self, B, device, always=False):
         """(int32 tensor | None, n_ints): the bucket workspace of ``dctr_embed_update`` / ``dctr_embed_segments`` -- zero
         before its first use, left ready by the kernels, so one tensor per (batch, device) serves every step.  Without
         the segment pre-pass it only pays for large batches, where a workgroup's scan over the unit's B ids is the
@@ -801,9 +788,7 @@ class EmbeddingPlan(object):
         mode = os.environ.get("DCTR_UPD_BUCKET", "auto")
         if not always and (mode == "0" or (mode != "1" and B < 8192)):
             return None, 0
-        # (slot: the "tower_seg" step topology alternates between two workspaces -- the pre-pass of step n runs on the
-        # side stream while the update of step n-1 may still be reading its own on the main stream)
-        key = (int(B), str(device)) if not slot else (int(B), str(device), int(slot))
+        key = (int(B), str(device))
         ws = self._upd_ws.get(key)
         if ws is not None:
             self._upd_ws[key] = self._upd_ws.pop(key)      # (least recently used goes first)
@@ -826,16 +811,12 @@ class EmbeddingPlan(object):
         import os
         return os.environ.get("DCTR_SEGMENTS", "1") != "0"
 
-    def launch_segments(self, ids_t, parts_t, B, X=None, before=None, fork=True, slot=0, join_before=True):
+    def launch_segments(self, ids_t, parts_t, B, X=None):
         """Enqueue the pre-pass for this forward's ids on the side stream.  Returns the handle the update passes to
         ``update_workspace_for``.  A workspace still marked by an earlier forward (whose backward never ran -- a
-        forward in train mode that was not followed by a backward) is taken over.
-        ``before(stream_handle)``: work that goes to the side stream ahead of the pre-pass -- the gather itself in the
-        "gather_side" step topology; the calling stream then waits for exactly that work (not for the pre-pass).
-        ``fork=False``: the side stream does not wait for the calling stream first (its own order -- behind the
-        previous step's update -- is all the gather needs)."""
+        forward in train mode that was not followed by a backward) is taken over."""
         device = ids_t.device
-        ws, ws_n = self.update_workspace(B, device, always=True, slot=slot)
+        ws, ws_n = self.update_workspace(B, device, always=True)
         dirty = getattr(ws, "_dctr_owner", None) is not None
 
         def enqueue(stream):
@@ -860,8 +841,6 @@ class EmbeddingPlan(object):
         _OWNER_TOKEN[0] += 1
         token = _OWNER_TOKEN[0]
         if device.type != "cuda":                  # (CPU stand-in: same calls, no streams)
-            if before is not None:
-                before(None)
             enqueue(None)
             ws._dctr_owner = token
             return (True, ws, token)
@@ -869,14 +848,7 @@ class EmbeddingPlan(object):
         side = self._seg_stream
         if side is None or side.device != device:
             side = self._seg_stream = _streams.side_stream(device, "seg")
-        if fork:
-            side.wait_stream(main)
-        if before is not None:
-            with torch.cuda.stream(side):
-                before(L.stream_handle(device))
-            if join_before:
-                main.wait_stream(side)      # (an event at the side stream's tail of NOW: the pre-pass comes behind it)
-            # (join_before=False: the caller orders the main stream behind `before`'s work itself -- dctr_step_wait)
+        side.wait_stream(main)
         with torch.cuda.stream(side):
             enqueue(L.stream_handle(device))
         ws._dctr_owner = token

@@ -23,18 +23,6 @@ captured step.
 
 The arithmetic is the two-launch path's, in its order: parameters after any number of steps are bit-identical
 (tests/test_gpu_step_engine.py).
-
-Round 6, an OPT-IN topology (``DCTR_STEP_TOPOLOGY=weights_flag``; bit-identical, measured slower than the default:
-``GatherStep.topology``):
-
-    main queue :  tower(k) -> dctr_embed_update(k) -> tower(k+1) ...
-    side queue :  [after tower(k)] dctr_mlp_train_wgrad_sync(k) -> [after update(k)] pre-pass of batch k+1
-
-What tower(k+1) needs from the side queue -- the dense parameters stepped by the weight-gradient launch of step k -- it waits
-for INSIDE the kernel, after it has staged its X tile and gathered its table rows: a word in memory the weight-gradient launch
-advances when its last reducer has stored the parameters (include/dctr.h, DCTR_SYNC_W_GEN).  The reduction is folded into the
-weight-gradient launch (a tile's last arriver sums the partial slabs in slab order: the same bits).  tower(k+1) then runs
-beside the weight gradients of step k, which read step k's activations: the activation buffers exist twice and alternate.
 """
 import contextlib
 import ctypes
@@ -56,11 +44,9 @@ def _r4(n):
 
 
 class _Buffers(object):
-    """Everything one batch size needs, allocated once: activations, gradients, workspaces, the tower descriptor.
-    ``alt``: a second set of what the tower launch writes and the weight-gradient launch reads (out, gx, fm_s, g_logit,
-    hs, dhs, ws, desc) -- the weights_flag topology alternates between the two; everything else is shared."""
+    """Everything one batch size needs, allocated once: activations, gradients, workspaces, the tower descriptor."""
     __slots__ = ("B", "out", "gx", "fm_s", "g_logit", "hs", "dhs", "ws", "ids_t", "parts_t", "desc", "upd_ws", "upd_n",
-                 "keep", "pinned", "den_t", "amax", "alt", "cnt")
+                 "keep", "pinned", "den_t", "amax")
 
 
 class GatherStep(object):
@@ -81,9 +67,6 @@ class GatherStep(object):
         self.stamp_i = 0          # boundaries around its tower launch (columns 0, 1) and its update (2, 3): dctr_stamp;
                                   # column 4: one more stamp right in front of column 0's (the cost of a stamp launch)
         self.steps_run = 0        # steps this engine enqueued (eager or captured): who asks whether it really ran
-        self._sync = None         # the weights_flag topology's sync block (include/dctr.h DCTR_SYNC_W_GEN / T_GEN)
-        self._parity = 0          # which activation set the next step writes
-        self._pool, self._pool_i = None, 0
 
     # ---- applicability ------------------------------------------------------------------------------------------
     @staticmethod
@@ -152,19 +135,6 @@ class GatherStep(object):
         b.upd_ws, b.upd_n = plan.update_workspace(B, dev, always=True)
         b.keep = (Ws, gWs, gbs, g_wo)
         b.pinned = False
-        # the second activation set (weights_flag topology) and the weight-gradient launch's arrival counters
-        a = _Buffers()
-        a.B = b.B
-        a.hs = [torch.empty_like(h) for h in b.hs]
-        a.dhs = [torch.empty_like(h) for h in b.hs]
-        a.desc = L.Mlp()
-        _mlp._fill(a.desc, meta, Ws, lds, bp, a.hs, a.dhs, gWs, gbs, self.w_out.reshape(-1), g_wo)
-        a.out, a.gx = torch.empty_like(b.out), torch.empty_like(b.gx)
-        a.fm_s = torch.empty_like(b.fm_s) if b.fm_s is not None else None
-        a.g_logit, a.ws = torch.empty_like(b.g_logit), torch.empty_like(b.ws)
-        b.alt = a
-        b.cnt = torch.zeros((max(1, lib.dctr_mlp_train_wgrad_counters(ctypes.byref(b.desc), int(B))),), dtype=torch.int32,
-                            device=dev)
         # Least recently used goes first -- but never a set a hipGraph was captured on: the graph holds raw addresses of
         # out / gx / hs / ws / ids_t / the update workspace and nothing else keeps them alive (a fit() over shards of many
         # ragged tail sizes used to push the full-batch set out from under its still-replaying graph: round-4 advisor
@@ -197,8 +167,6 @@ class GatherStep(object):
         a multi-step hipGraph): its pre-pass is enqueued on the side queue right behind this step's update, so that it
         runs in the shadow of the queue hop back to the main queue instead of beside the next tower launch (measured:
         the pre-pass's 1118 workgroups beside the tower cost the tower 4 of its 53 us, profiles/r04_*timeline*)."""
-        if xb.device.type == "cuda" and self.topology() == "weights_flag":
-            return self._step_flag(xb, yb, mode, next_xb)
         lib = L.lib()
         model, slab = self.model, self.slab
         plan = model.model_plan()
@@ -236,9 +204,8 @@ class GatherStep(object):
         plan.point_step_buffers(b.den_t, b.amax)
         ld = plan.ld_out
         ld_s = b.fm_s.stride(0) if b.fm_s is not None else 0
-        serial = os.environ.get("DCTR_STEP_TOPOLOGY", "update_side") == "serial" or not cuda
         main = torch.cuda.current_stream(dev) if cuda else None
-        side = _streams.side_stream(dev, "seg") if (cuda and not serial) else None
+        side = _streams.side_stream(dev, "seg") if cuda else None     # (no GPU -- the CPU stand-in of the tests: one queue)
         on_side = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
         # (did the previous step already enqueue THIS batch's pre-pass?  Only ever inside one hipGraph capture: the token
         # names the batch's memory, the buffers and the capture)
@@ -307,141 +274,6 @@ class GatherStep(object):
         finally:
             slab.inline_done = True
             slab.end_inline_step()
-        return loss, y_pred
-
-    # ---- round 6: tower -> update -> tower on one queue, the weights handed over through a word in memory --------------
-    @staticmethod
-    def topology():
-        """update_side (default): the round-4 two-queue step.  weights_flag (round 6, opt-in): tower -> update on ONE queue,
-        the dense parameters handed to the next tower launch through a word in memory (_step_flag) -- bit-identical
-        (tests/test_gpu_step_engine.py) and measured SLOWER, 0.107 against 0.090 ms per step: every cross-queue edge of a
-        hipGraph costs the queues it touches 6-12 us, and this arrangement still has three of them per step on the main queue
-        (profiles/r06_step_edges.txt; DESIGN.md section 3 has the whole account, including the edge-free two-graph variant
-        that was built, measured at 0.104 ms and removed)."""
-        t = os.environ.get("DCTR_STEP_TOPOLOGY", "update_side")
-        return t if t in ("weights_flag", "update_side", "serial") else "update_side"
-
-    def _event(self):
-        """events that live as long as the engine, handed out round-robin (see _join_event)"""
-        if self._pool is None:
-            self._pool = [torch.cuda.Event() for _ in range(12)]
-        self._pool_i = (self._pool_i + 1) % len(self._pool)
-        return self._pool[self._pool_i]
-
-    def _step_flag(self, xb, yb, mode, next_xb=None):
-        lib = L.lib()
-        model, slab = self.model, self.slab
-        plan = model.model_plan()
-        dev = xb.device
-        B = xb.shape[0]
-        b = self._buffers(B, dev)
-        self.steps_run += 1
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            b.pinned = True
-        a = b if self._parity == 0 else b.alt      # the activation set of this step
-        self._parity ^= 1
-        cplan = plan.bind(dev)
-        y = yb.reshape(-1)
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.float().contiguous()
-        y_pred = torch.empty((B,), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        kind = plan.update[0]
-        opt = L.UPD_ADAGRAD if kind == "adagrad" else L.UPD_SGD
-        lr = float(plan.update[1])
-        eps = float(plan.update[2]) if kind == "adagrad" else 0.0
-        if not slab.begin_inline_step(mode[0], mode[1], mode[2] if len(mode) > 2 else 0.0):
-            raise RuntimeError("the gather step needs a plain SGD / Adagrad dense optimizer")
-        inline = slab.inline
-        bias = model.out.bias
-        g_bias = slab.grad_of(bias)
-        lw = plan.wide_dense_weight
-        g_wd = slab.grad_of(lw) if lw is not None else None
-        err = plan.err_flag(dev)
-        ws_u = b.upd_ws
-        if getattr(ws_u, "_dctr_owner", None) is not None:      # an abandoned pre-pass of the autograd route left counts
-            ws_u.zero_()
-            ws_u._dctr_owner = None
-            self._prepassed = None
-        if self._sync is None or self._sync.device != dev:
-            self._sync = torch.zeros((L.SYNC_INTS,), dtype=torch.int32, device=dev)
-        units, n_units = plan.units_ptr(), plan.n_grid_units
-        plan.point_step_buffers(b.den_t, b.amax)
-        ld = plan.ld_out
-        ld_s = a.fm_s.stride(0) if a.fm_s is not None else 0
-        main = torch.cuda.current_stream(dev)
-        side = _streams.side_stream(dev, "seg")
-        token = (xb.data_ptr(), xb.stride(0), B, id(b), bool(capturing))
-        have_prepass = self._prepassed is not None and self._prepassed == token and token[4]
-        self._prepassed = None
-        timeout_us = int(os.environ.get("DCTR_STEP_WAIT_US", "2000000"))
-        dbg = int(os.environ.get("DCTR_DBG_EDGES", "0"))     # TIMING EXPERIMENTS ONLY: drop graph edges (wrong results)
-        ok = False
-        try:
-            if not have_prepass:
-                side.wait_stream(main)       # X is complete; (first step of a capture: the side queue joins the capture)
-                with torch.cuda.stream(side):
-                    self._prepass(b, cplan, xb, B, L.stream_handle(dev))
-            ev_pre = self._event()
-            ev_pre.record(side)              # this batch's pre-pass (enqueued here or by the previous step) is done
-            mh = L.stream_handle(dev)
-            if self.timing_tower is not None:
-                self.timing_tower[0].record(main)
-            L.check(lib.dctr_embed_tower_train_step_sync(
-                cplan, _ptr(xb), xb.stride(0), ctypes.byref(a.desc), B, 1 if self.want_fm else 0, _ptr(bias), _ptr(y),
-                _ptr(y_pred), _ptr(a.g_logit), _ptr(a.gx), ld, _ptr(a.out), ld, _ptr(a.fm_s), ld_s, _ptr(err), _ptr(a.ws),
-                _ptr(self._sync), timeout_us, mh), "dctr_embed_tower_train_step_sync")
-            if self.timing_tower is not None:
-                self.timing_tower[1].record(main)
-            ev_t = self._event()
-            ev_t.record(main)
-            # side queue: the weight gradients with their reduction and the dense optimizer step; the launch's last reducer
-            # advances the weights' generation, which the NEXT tower launch waits for in its kernel
-            if not (dbg & 4):
-                side.wait_event(ev_t)
-            with torch.cuda.stream(side):
-                L.check(lib.dctr_mlp_train_wgrad_sync(ctypes.byref(a.desc), _ptr(a.out), ld, B, _ptr(a.g_logit), _ptr(a.ws),
-                                                      _ptr(loss), _ptr(g_bias), ctypes.byref(inline), _ptr(self._sync),
-                                                      _ptr(b.cnt), L.stream_handle(dev)), "dctr_mlp_train_wgrad_sync")
-            # main queue: the update, right behind the tower (its pre-pass finished long ago: an edge with slack)
-            if not (dbg & 2):
-                main.wait_event(ev_pre)
-            if self.timing is not None:
-                self.timing[0].record(main)
-            L.check(lib.dctr_embed_update(cplan, units, n_units, plan.max_vocab, _ptr(b.ids_t), _ptr(b.parts_t), B,
-                                          _ptr(a.gx), ld, _ptr(a.out), ld, _ptr(a.fm_s), ld_s,
-                                          _ptr(a.g_logit) if self.want_fm else None,
-                                          _ptr(a.g_logit) if plan.has_wide else None, 1, opt, lr, eps, _ptr(xb),
-                                          xb.stride(0), _ptr(g_wd), ctypes.byref(inline) if g_wd is not None else None,
-                                          _ptr(ws_u), b.upd_n, 1, mh), "dctr_embed_update")
-            if self.timing is not None:
-                self.timing[1].record(main)
-            nxt = next_xb if (next_xb is not None and capturing and tuple(next_xb.shape) == tuple(xb.shape) and
-                              next_xb.dtype == xb.dtype and next_xb.stride() == xb.stride()) else None
-            if nxt is not None:
-                # the next batch's pre-pass on the side queue, behind the weight gradients and behind THIS update (which
-                # reads the buffers the pre-pass rewrites)
-                if not (dbg & 1):
-                    ev_u = self._event()
-                    ev_u.record(main)
-                    side.wait_event(ev_u)
-                with torch.cuda.stream(side):
-                    self._prepass(b, cplan, nxt, B, L.stream_handle(dev))
-                self._prepassed = (nxt.data_ptr(), nxt.stride(0), B, id(b), True)
-            else:
-                # the last step of a captured group, or an eager step: whatever follows on the caller's queue (the loss, a
-                # predict, another model) sees the dense parameters stepped
-                main.wait_stream(side)
-            ok = True
-        finally:
-            slab.inline_done = True
-            slab.end_inline_step()
-            if not ok and not capturing:
-                # a launch of the pair may be missing: the generations could disagree from here on -- start over
-                torch.cuda.synchronize(dev)
-                self._sync.zero_()
-                b.cnt.zero_()
         return loss, y_pred
 
     def _join_event(self):

@@ -803,17 +803,6 @@ class BaseModel(nn.Module):
         if plan.update[0] in ("sgd", "adagrad") and os.environ.get("DCTR_INLINE_OPT", "1") != "0" and \
                 plan.segments_enabled():
             slab.begin_inline_step(mode[0], mode[1], mode[2] if len(mode) > 2 else 0.0)
-            topo = os.environ.get("DCTR_STEP_TOPOLOGY", "update_side")
-            slab.wgrad_side = topo in ("tower_side", "tower_seg")
-            slab.wgrad_on_seg = topo == "tower_seg"
-            slab.gather_side = topo in ("gather_side", "flags")
-            # ("flags" needs its sync block to exist before a hipGraph capture begins: a capture without an eager step
-            # in front of it falls back to the event edges of "gather_side")
-            slab.flag_sync = topo == "flags" and xb.is_cuda and \
-                (slab._sync is not None or not torch.cuda.is_current_stream_capturing())
-            if slab.flag_sync:
-                slab.sync_block(xb.device)
-                plan._sync_owner = slab
         reg = None
         try:
             loss, y_pred = self.fused_loss(xb, yb, slab)
@@ -825,26 +814,12 @@ class BaseModel(nn.Module):
                 if rv is not None:
                     reg = rv if reg is None else reg + rv
             loss.backward(gradient=st["one"])       # a resident 1.0: no fill launch per step
-        except BaseException:
-            if slab.flag_sync and not torch.cuda.is_current_stream_capturing():
-                try:                 # a step interrupted between a signal and its wait: start the pairs over
-                    slab.check_sync(reset=True)
-                except RuntimeError:
-                    pass
-            raise
         finally:
             self._grad_sink = None
             plan.dense_sink = None
             slab.overlap = False
-            after = getattr(slab, "after_update", None)
-            if after is not None:         # (no embedding update was launched behind the tower: fork now)
-                slab.after_update = None
-                after()
             slab.end_inline_step()
-            if not ((slab.wgrad_side or slab.gather_side) and getattr(self, "_defer_dense_join", False)):
-                # (inside a multi-step hipGraph the captured steps but the last leave the forked weight-gradient /
-                # optimizer kernels unjoined: the next step's tower launch is the first reader of what they write)
-                slab.join()
+            slab.join()
         slab.step(*mode)
         total = loss.detach().reshape(1)
         if reg is not None:

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 25
+#define DCTR_ABI_VERSION 26
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -98,7 +98,7 @@ typedef struct dctr_vunit {
 } dctr_vunit_t;
 
 /* host struct; `slots`, `vunits`, `am_deep_off`, `am_wide_off`, `den_t`, `amax` are DEVICE pointers, `h_*` host arrays.
- * den_t / amax are PER-STEP buffers the caller points at before each call (like dctr_plan_t.step_sync):
+ * den_t / amax are PER-STEP buffers the caller points at before each call:
  *   den_t [n_den, B] float  written by dctr_embed_ids, read by dctr_embed_update
  *   amax  [B, ld_amax] u8   written by dctr_embed_fwd (arg-max position per element of every max-pooled field, first
  *                           maximum wins like torch.max), read by dctr_embed_update                                  */
@@ -146,8 +146,6 @@ typedef struct dctr_plan {
   int32_t vec;                /* 4, 2 or 1: every deep dim, out_off, ld and base pointer is a        */
                               /* multiple of `vec` floats -- lets rows move as dwordx4/x2            */
   int32_t flags;              /* DCTR_PLAN_* : facts about the device arrays the host cannot see     */
-  int32_t* step_sync;         /* nullable: dctr_embed_fwd signals DCTR_SYNC_GATHER in this block when its outputs  */
-                              /* have left the chip's caches (see dctr_step_wait)                                  */
   const uint64_t* out_chunks; /* nullable, device: dctr_embed_fwd writes output row b (and its wide logit, which must lie   */
   int32_t chunk_rows;         /* inside the row: wide = out + k, ld_wide = ld_out) to (float*)out_chunks[b / chunk_rows] +  */
   int32_t pad_;               /* (b % chunk_rows) * ld_out instead of out + b * ld_out: the owner's gather of the sharded   */
@@ -665,7 +663,6 @@ typedef struct dctr_mlp {
   float* g_w_out;     /* [N_last] nullable */
   int32_t n_layers;
   int32_t pad_;
-  int32_t* step_sync; /* nullable: dctr_mlp_train_step's first launch signals DCTR_SYNC_TOWER (gx and g_logit complete) */
 } dctr_mlp_t;
 size_t dctr_sizeof_mlp(void);
 #ifdef DCTR_DIAG
@@ -720,62 +717,6 @@ int dctr_embed_tower_train_step(const dctr_plan_t* plan, const float* X, int64_t
                                 float* gx, int64_t ld_gx, float* out, int64_t ld_out, float* fm_s, int64_t ld_s,
                                 int32_t* err, float* workspace, dctr_stream_t stream);
 
-/* The same two launches for a step whose critical cycle is tower -> embedding update -> next tower on ONE queue, with the
- * weight gradients on a second queue (round 6; reference: the optimizer step of basemodel.py:262 must precede the next
- * forward of basemodel.py:246 -- here that order is kept by a word in memory, see DCTR_SYNC_W_GEN below):
- *   dctr_mlp_train_wgrad_sync        dctr_mlp_train_wgrad as ONE launch: a tile's last workgroup to arrive sums the tile's
- *                                    partial slabs in slab order and steps the parameters (the arithmetic of the separate
- *                                    reduction launch, bit for bit), then the launch advances sync[DCTR_SYNC_W_GEN].
- *                                    counters: dctr_mlp_train_wgrad_counters(m, B) int32, zero before the first call.
- *   dctr_embed_tower_train_step_sync dctr_embed_tower_train_step that requests no dense parameter (tower weights, biases,
- *                                    the projection, `bias`) before sync[DCTR_SYNC_W_GEN] has caught up with the number of
- *                                    tower launches finished on this block; a wait that exceeds timeout_us raises bit 2 (4)
- *                                    of *err and goes on.  Results: those of the plain calls, bit for bit.                */
-size_t dctr_mlp_train_wgrad_counters(const dctr_mlp_t* m, int32_t B);
-int dctr_mlp_train_wgrad_sync(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, const float* g_logit,
-                              float* workspace, float* loss, float* g_bias, const dctr_dense_step_t* step, int32_t* sync,
-                              int32_t* counters, dctr_stream_t stream);
-int dctr_embed_tower_train_step_sync(const dctr_plan_t* plan, const float* X, int64_t ldx, const dctr_mlp_t* m, int32_t B,
-                                     int32_t want_fm, const float* bias, const float* y, float* y_pred, float* g_logit,
-                                     float* gx, int64_t ld_gx, float* out, int64_t ld_out, float* fm_s, int64_t ld_s,
-                                     int32_t* err, float* workspace, int32_t* sync, int32_t timeout_us,
-                                     dctr_stream_t stream);
-
-/* ---- device-side dependencies between the two queues of a train step ---------------------------------------------
- * A dependency that crosses hardware queues costs 11-12 us through hipGraph / stream events on this stack, 4.6 us through
- * a word in memory (tools/micro/hopbench.hip), and the DeepFM step's critical cycle crosses twice (tower -> update,
- * gather -> tower: 24 of its 99 us).  So the producer kernels can SIGNAL and a one-wave kernel in front of the consumer
- * WAITS:
- *   sync block: DCTR_SYNC_INTS int32, zero before first use, one per model.  For each signal s (DCTR_SYNC_TOWER /
- *     DCTR_SYNC_GATHER): a generation counter the producer's LAST workgroup advances -- after every workgroup has
- *     stored what the consumer reads with write-through stores and waited for them -- and an epoch counter the waiter
- *     advances once per call: the n-th wait returns when the n-th signal has been given.
- *   dctr_step_wait enqueues the waiter (1 workgroup of 64 threads: it cannot keep a producer from being scheduled).  It
- *     gives up after timeout_us (and raises bit s of the block's error word, DCTR_SYNC_ERR): a kernel stream that is
- *     serialised by a profiler collecting counters, or a producer that was never launched, costs time, not a hang.
- * The consumer is launched behind the waiter on the same stream; its own start-of-kernel acquire does the rest.
- * Signals and waits must pair up one to one (the fused train step does; dctr_step_sync is for nothing else).        */
-#define DCTR_SYNC_TOWER 0
-#define DCTR_SYNC_GATHER 1
-#define DCTR_SYNC_UPDATE 2   /* given by dctr_step_signal behind dctr_embed_update (the "fused_flags" step topology) */
-#define DCTR_SYNC_ERR 12     /* index of the error word */
-#define DCTR_SYNC_INTS 32    /* [4 s, 4 s + 4): signal s' generation / epoch / arrivals / stamp; [16 + 2 s, +2): its waiter's stamps */
-/* Round 6 -- the weights' hand-over INSIDE the waiting kernel (no waiter launch, no graph edge): words of the same block.
- *   W_GEN  weight steps finished: advanced by the last reducer of dctr_mlp_train_wgrad_sync, after every dense parameter
- *          it steps has been stored write-through and waited for;
- *   T_GEN  tower launches finished: advanced by the last workgroup of dctr_embed_tower_train_step_sync.
- * A tower launch may start while the previous step's weight-gradient launch still runs on another queue: it stages its X
- * tile and gathers its table rows (which only need the embedding update, ordered in front of it on its own queue), then
- * waits until W_GEN >= T_GEN (as read at its start) before it requests the first dense parameter.  The two calls must
- * alternate strictly (tower, weight gradients, tower, ...) on one sync block; the block is zero before the first call.  */
-#define DCTR_SYNC_W_GEN 24
-#define DCTR_SYNC_W_ARR 25
-#define DCTR_SYNC_T_GEN 26
-#define DCTR_SYNC_T_ARR 27
-int dctr_step_wait(int32_t* sync, int32_t signal, int32_t timeout_us, dctr_stream_t stream);
-/* The signal as a one-thread launch of its own on the producer's queue, behind the producer (whose end-of-kernel
- * write-back makes its stores visible first): for a producer that cannot signal from inside its kernel.            */
-int dctr_step_signal(int32_t* sync, int32_t signal, dctr_stream_t stream);
 /* *dst (device) = the 100 MHz device wall clock at the moment a one-thread launch runs on `stream`: put between two kernels
  * of a queue it dates their boundary -- the only way to time a kernel INSIDE a hipGraph replay (bench.py: the graph-replayed
  * duration of the step's dominant kernels).                                                                           */

@@ -99,9 +99,6 @@ class _Core(object):
     def dctr_mlp_train_workspace_floats(self, mref, B):
         return 16
 
-    def dctr_mlp_train_wgrad_counters(self, mref, B):
-        return 4
-
     @staticmethod
     def _dense_step(step, gptr, n):
         """dctr_dense_step_t applied to the n parameters behind the gradient at gptr (include/dctr.h)"""
@@ -178,9 +175,6 @@ class _Core(object):
         return 0
 
     def dctr_stamp(self, dst, stream):
-        return 0
-
-    def dctr_step_signal(self, sync, signal, stream):
         return 0
 
     # ---- head ---------------------------------------------------------------------------------------------

@@ -62,11 +62,8 @@ def _data(vocab, F, n_dense, B, n_batches, seed=7, pooled=None):
     return X, y
 
 
-def _run(engine, kind, vocab, opt, steps, graphed, B=4096, F=26, D=16, n_dense=13, hidden=(256, 128), topo=None,
-         pooled=None):
+def _run(engine, kind, vocab, opt, steps, graphed, B=4096, F=26, D=16, n_dense=13, hidden=(256, 128), pooled=None):
     os.environ["DCTR_STEP_ENGINE"] = "1" if engine else "0"
-    if topo:
-        os.environ["DCTR_STEP_TOPOLOGY"] = topo
     try:
         m = _model(kind, vocab, opt, F, D, n_dense, hidden, pooled)
         X, y = _data(vocab, F, n_dense, B, 8, pooled=pooled)
@@ -113,7 +110,6 @@ def _run(engine, kind, vocab, opt, steps, graphed, B=4096, F=26, D=16, n_dense=1
         return sd, ost, torch.stack([l.reshape(()) for l in losses]).cpu(), [p.cpu() for p in preds]
     finally:
         os.environ.pop("DCTR_STEP_ENGINE", None)
-        os.environ.pop("DCTR_STEP_TOPOLOGY", None)
 
 
 def _same(a, b, what):
@@ -161,19 +157,6 @@ def test_engine_runs_pooled_fields_graph_replayed():
     two-launch step (whose pooled lookup and sorted update are pinned to the reference's goldens)."""
     _same(_run(False, "deepfm", 3000, "adagrad", 42, True, pooled=(8, 5)),
           _run(True, "deepfm", 3000, "adagrad", 42, True, pooled=(8, 5)), "deepfm + pooled")
-
-
-@pytest.mark.parametrize("topo", ["serial", "weights_flag"])
-def test_engine_topologies(topo):
-    """Every way of enqueueing the step leaves the default's bits.  Round 6: ``weights_flag`` (tower -> update on one queue,
-    the dense parameters handed to the next tower launch through DCTR_SYNC_W_GEN, the reduction folded into the
-    weight-gradient launch: _hip/step.py) -- opt-in, slower than the default, kept exact."""
-    ref = _run(True, "deepfm", 3000, "adagrad", 42, True)
-    _same(ref, _run(True, "deepfm", 3000, "adagrad", 42, True, topo=topo), topo)
-    if topo == "weights_flag":
-        _same(_run(True, "deepfm", 3000, "sgd", 22, True, pooled=(4, 3, 5)),
-              _run(True, "deepfm", 3000, "sgd", 22, True, topo=topo, pooled=(4, 3, 5)), topo + " + pooled")
-        _same(_run(True, "wdl", 3000, "sgd", 6, False), _run(True, "wdl", 3000, "sgd", 6, False, topo=topo), topo + " eager")
 
 
 def test_engine_long_run_on_large_tables():
@@ -239,22 +222,3 @@ def test_kernel_outputs_equal_the_two_launches():
         assert torch.equal(a, c)
     for a, c in zip(b.dhs, dh0):
         assert torch.equal(a, c)
-
-
-def test_step_signal_releases_a_waiter():
-    """dctr_step_signal (the signalling half as a launch of its own) against dctr_step_wait: the n-th wait returns when the
-    n-th signal has been given; no time-out bit is raised."""
-    from deepctr_torch._hip import lib as L
-    lib = L.lib()
-    sync = torch.zeros(L.SYNC_INTS, dtype=torch.int32, device=DEV)
-    side = torch.cuda.Stream()
-    P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
-    torch.cuda.synchronize()
-    for _ in range(3):
-        L.check(lib.dctr_step_wait(P(sync), L.SYNC_UPDATE, 20000, L.stream_handle(sync.device)))
-        with torch.cuda.stream(side):
-            L.check(lib.dctr_step_signal(P(sync), L.SYNC_UPDATE, ctypes.c_void_p(side.cuda_stream)))
-    torch.cuda.synchronize()
-    v = sync.cpu()
-    assert int(v[L.SYNC_ERR]) == 0
-    assert int(v[4 * L.SYNC_UPDATE]) == 3 and int(v[4 * L.SYNC_UPDATE + 1]) == 3
