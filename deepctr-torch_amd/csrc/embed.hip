@@ -175,6 +175,9 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
     return reinterpret_cast<float*>(P.out_chunks[r]) + static_cast<int64_t>(row - r * P.chunk_rows) * ldo;
   };
   float* orow = out ? row_of(b) : nullptr;
+  // DCTR_PLAN_WIDE_PER_FIELD: the first-order weights go out per field (wrow[f]), only the dense half is summed (wrow[n_wide])
+  const bool wpf = (P.flags & DCTR_PLAN_WIDE_PER_FIELD) != 0;
+  float* wrow = wide ? wide + static_cast<int64_t>(b) * ldw : nullptr;
 
   // side output for dctr_embed_update: the ids of this tile, transposed to [unit][b] (64-byte runs)
   // (+ parts_t: the partition of dctr_embed_update each entry belongs to, so that its workgroups compare 16-bit tags
@@ -266,11 +269,21 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
   }
 
   if (wide) {
+    if (wpf) {
 #pragma unroll
-    for (int k = 0; k < WCH; ++k) ws += ((k * kNW + wv_id) * LPR + gl < nwf) ? wval[k] : 0.f;
+      for (int k = 0; k < WCH; ++k) {
+        const int f = (k * kNW + wv_id) * LPR + gl;
+        if (f < nwf && valid) stg_f32(wrow + f, wval[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < WCH; ++k) ws += ((k * kNW + wv_id) * LPR + gl < nwf) ? wval[k] : 0.f;
+    }
     for (int f = (WCH * kNW + wv_id) * LPR + gl; f < nwf; f += kNW * LPR) {  // > 8*LPR wide fields
       const dctr_field_t& fd = T.wide[f];
-      ws += ldg_f32(fd.table + checked(raw_id(xr, fd.col), fd.vocab, bad) * row_ld(fd));
+      const float wv = ldg_f32(fd.table + checked(raw_id(xr, fd.col), fd.vocab, bad) * row_ld(fd));
+      if (!wpf) ws += wv;
+      else if (valid) stg_f32(wrow + f, wv);
     }
     for (int f = P.n_wide_fixed + wv_id * LPR + gl; f < P.n_wide; f += kNW * LPR) {  // pooled VarLen
       const dctr_field_t& fd = T.wide[f];
@@ -279,7 +292,9 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
         const int off = ldg_i32(am_wide_off + f);
         if (off >= 0) am = amax + static_cast<int64_t>(b) * ld_am + off;
       }
-      ws += pool_field<1>(fd, xr, 0, true, bad, am).v[0];
+      const float wv = pool_field<1>(fd, xr, 0, true, bad, am).v[0];
+      if (!wpf) ws += wv;
+      else if (valid) stg_f32(wrow + f, wv);
     }
     if (P.wdense_w)
       for (int j = wv_id * LPR + gl; j < P.n_wdense; j += kNW * LPR)
@@ -325,7 +340,8 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
       }
       if (wide) {
         wt = group_sum<LPR>(wt);
-        if (gl == 0 && valid) stg_f32(P.out_chunks ? orow + (wide - out) : wide + static_cast<int64_t>(b) * ldw, wt);
+        if (gl == 0 && valid)
+          stg_f32(P.out_chunks ? orow + (wide - out) : wide + static_cast<int64_t>(b) * ldw + (wpf ? P.n_wide : 0), wt);
       }
     }
   }
@@ -422,16 +438,20 @@ __global__ __launch_bounds__(kThreads) void k_embed_bwd(dctr_plan_t P, const flo
 
   // ---- wide tables: d wide[b] / d w_f[id] = 1 --------------------------------------------------
   if (gwide) {
-    const float gw = ldg_f32(gwide + b);
+    // DCTR_PLAN_WIDE_PER_FIELD: g_wide is [B, n_wide + 1], field f's gradient in column f
+    const bool wpf = (P.flags & DCTR_PLAN_WIDE_PER_FIELD) != 0;
+    const float* gwrow = wpf ? gwide + static_cast<int64_t>(b) * (P.n_wide + 1) : gwide + b;
+    const float gw0 = wpf ? 0.f : ldg_f32(gwrow);
     for (int f = wv_id * LPR + gl; f < P.n_wide_fixed; f += kNW * LPR) {
       const dctr_field_t& fd = T.wide[f];
       const int64_t id = checked(raw_id(xr, fd.col), fd.vocab, bad);
+      const float gw = wpf ? ldg_f32(gwrow + f) : gw0;
       atomic_add_f32((SGD ? fd.table + id * row_ld(fd) : fd.gacc + id), scale * gw);
     }
     for (int f = P.n_wide_fixed + wv_id * LPR + gl; f < P.n_wide; f += kNW * LPR) {
       const dctr_field_t& fd = T.wide[f];
       Strip<1> g1;
-      g1.v[0] = gw;
+      g1.v[0] = wpf ? ldg_f32(gwrow + f) : gw0;
       unpool_field<1, SGD>(fd, xr, 0, true, g1, scale);
     }
   }
@@ -605,6 +625,10 @@ extern "C" int dctr_embed_fwd(const dctr_plan_t* plan, const float* X, int64_t l
                               uint16_t* parts_t, float* fm_s, int64_t ld_s, dctr_stream_t stream) {
   if (int rc = check_plan(plan, X, ldx, B)) return rc;
   if (wide && ld_wide < 1) return DCTR_EINVAL;
+  if (plan->flags & DCTR_PLAN_WIDE_PER_FIELD) {
+    if (wide && ld_wide < plan->n_wide + 1) return DCTR_EINVAL;
+    if (plan->out_chunks) return DCTR_ENOSUP;   // (the sharded exchange carries one wide column per row)
+  }
   if (B == 0) return DCTR_OK;
   if (fm && (plan->emb_dim <= 0 || !out)) return DCTR_EINVAL;  // FM needs the deep rows
   if (fm_s && (plan->emb_dim <= 0 || !out || ld_s < plan->emb_dim)) return DCTR_EINVAL;

@@ -2850,6 +2850,7 @@ int lpr_shift_of(int D) {
 // the plans / towers the fused gather stage takes (everything else keeps dctr_embed_fwd + dctr_mlp_train_step)
 int gather_envelope(const dctr_plan_t* p, const dctr_mlp_t* m, int32_t B, const TrainGeom& T) {
   if (!p || !p->deep || p->n_deep < 1 || p->n_deep_fixed < 1) return DCTR_ENOSUP;
+  if (p->flags & DCTR_PLAN_WIDE_PER_FIELD) return DCTR_ENOSUP;   // (the fused gather sums the first-order weights)
   // pooled VarLen fields (sum / mean / max): their positions listed in the ext block, at most four 16-byte pieces and one
   // wide value per thread of the 16-sample tile
   const bool pooled = p->n_deep != p->n_deep_fixed || p->n_wide != p->n_wide_fixed;

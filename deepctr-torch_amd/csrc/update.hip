@@ -746,6 +746,8 @@ int embed_update_impl(const dctr_plan_t* plan, const int32_t* units, int32_t n_u
     if (x->ld_amax > 0 && !x->amax) return DCTR_EINVAL;
   }
   if (g_wide && ld_gw < 1) return DCTR_EINVAL;
+  const bool wpf = (plan->flags & DCTR_PLAN_WIDE_PER_FIELD) != 0;
+  if (wpf && g_wide && ld_gw < plan->n_wide + 1) return DCTR_EINVAL;
   if (g_wdense && (!X || !g_wide || plan->n_wdense <= 0 || !plan->wdense_cols)) return DCTR_EINVAL;
   if (B == 0) return DCTR_OK;
   if (opt != DCTR_UPD_SGD && opt != DCTR_UPD_ADAGRAD && opt != DCTR_UPD_ACCUM && opt != DCTR_UPD_LAZY) return DCTR_EINVAL;
@@ -770,6 +772,7 @@ int embed_update_impl(const dctr_plan_t* plan, const int32_t* units, int32_t n_u
   a.deep = plan->deep; a.wide = plan->wide; a.units = units; a.ids_t = ids_t;
   a.parts_t = nullptr;
   a.gout = g_out; a.fm_s = fm_s; a.gfm = g_fm; a.gwide = g_wide; a.ldgw = ld_gw;
+  a.wpf = wpf ? 1 : 0; a.gwd_col = wpf ? plan->n_wide : 0;
   a.ldg = ld_g; a.lds_ = ld_s;
   a.out = out; a.ldo = ld_out;
   a.lr = lr; a.eps = eps;

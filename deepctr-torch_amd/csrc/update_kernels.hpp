@@ -68,6 +68,8 @@ struct UpdArgs {
   const float* gfm;      // [B] nullable
   const float* gwide;    // [B] (stride ldgw) nullable
   int64_t ldgw;
+  int32_t wpf;           // DCTR_PLAN_WIDE_PER_FIELD: wide field f's gradient lives in column f of a gwide row ...
+  int32_t gwd_col;       // ... and the dense half's (wdense_column) in column n_wide; 0 / 0 otherwise
   int64_t ldg, lds_;
   int32_t n_units, B, P, bbits;   // P partitions per unit (any positive number)
   uint64_t pmagic;                // floor(2^pshift / P) + 1: id / P == (id * pmagic) >> pshift for 0 <= id < 2^31
@@ -265,6 +267,7 @@ __device__ __forceinline__ void split_id(const UpdArgs& A, const UnitCtx& U, uin
 // One entry of a general unit, decoded: sample, the deep field's slice, the pooling weight's ingredients.
 struct EntryDesc {
   int b, goff, pool, t, den, am_deep, am_wide;
+  int wcol;   // column of the entry's wide gradient in a gwide row (0 unless DCTR_PLAN_WIDE_PER_FIELD)
 };
 template <bool GEN>
 __device__ __forceinline__ EntryDesc entry_desc(const UpdArgs& A, const dctr_uslot_t* sl, int v, int goff_simple) {
@@ -279,6 +282,7 @@ __device__ __forceinline__ EntryDesc entry_desc(const UpdArgs& A, const dctr_usl
     E.den = d.den;
     E.am_deep = d.am_deep;
     E.am_wide = d.am_wide;
+    E.wcol = (A.wpf && d.wfield >= 0) ? d.wfield : 0;
   } else {
     E.b = v;
     E.goff = goff_simple;
@@ -287,6 +291,7 @@ __device__ __forceinline__ EntryDesc entry_desc(const UpdArgs& A, const dctr_usl
     E.den = -1;
     E.am_deep = -1;
     E.am_wide = -1;
+    E.wcol = 0;
   }
   return E;
 }
@@ -335,7 +340,8 @@ __device__ __forceinline__ void wdense_column(const UpdArgs& A, int j) {
   float acc = 0.f;
 #pragma unroll 8
   for (int b = tid; b < A.B; b += kThreads)
-    acc += ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw) * ldg_f32(A.X + static_cast<int64_t>(b) * A.ldx + col);
+    acc += ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw + A.gwd_col) *
+           ldg_f32(A.X + static_cast<int64_t>(b) * A.ldx + col);
   acc = wave_sum(acc);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
@@ -377,7 +383,7 @@ __device__ __forceinline__ void gen_entry(const UpdArgs& A, const EntryDesc& E, 
     }
   }
   if (wide_lane) {
-    gw = ldg_f32(A.gwide + b * A.ldgw);
+    gw = ldg_f32(A.gwide + b * A.ldgw + E.wcol);
     if (E.pool == DCTR_POOL_MAX) amw = *(const DCTR_GLOBAL uint8_t*)(A.amax + b * A.ld_am + E.am_wide);
   }
   if (E.pool == DCTR_POOL_MEAN && (deep || wide_lane)) den = ldg_f32(A.den_t + static_cast<int64_t>(E.den) * A.B + b);
@@ -490,6 +496,8 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
   const uint32_t bmask = (1u << U.vbits) - 1u;
   const bool deep_on = (di >= 0) && (A.gout || A.gfm);
   const bool wide_on = (wi >= 0) && A.gwide;
+  // (simple units: the unit's wide field is its column of a per-field gwide row)
+  [[maybe_unused]] const float* gwbase = wide_on ? A.gwide + (A.wpf ? wi : 0) : nullptr;
   const bool lane_on = deep_on && (e0 < fd.dim);
   const int goff = deep_on ? fd.out_off + (lane_on ? e0 : 0) : 0;
   const bool fold = (A.gfm != nullptr);
@@ -518,7 +526,7 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
         for (int k = 0; k < VEC; ++k) h.v[k] += gf * S.v[k];
       }
     }
-    if (wide_on && gl == 0) gw = ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw);
+    if (wide_on && gl == 0) gw = ldg_f32(gwbase + static_cast<int64_t>(b) * A.ldgw);
   };
   // the strips of a row this lane may update: w (table, or gacc in accumulate mode), s (Adagrad state), e (the
   // table strip FM's fold needs; = w unless accumulating)
@@ -1089,6 +1097,8 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
   const uint32_t bmask = (1u << U.vbits) - 1u;
   const bool deep_on = (di >= 0) && (A.gout || A.gfm);
   const bool wide_on = (wi >= 0) && A.gwide;
+  // (simple units: the unit's wide field is its column of a per-field gwide row)
+  [[maybe_unused]] const float* gwbase = wide_on ? A.gwide + (A.wpf ? wi : 0) : nullptr;
   const bool lane_on = deep_on && (e0 < fd.dim);
   const int goff = deep_on ? fd.out_off + (lane_on ? e0 : 0) : 0;
   const bool fold = (A.gfm != nullptr);
@@ -1147,7 +1157,7 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
           gf = ldg_f32(A.gfm + b);
         }
       }
-      if (wide_on && gl == 0) gw = ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw);
+      if (wide_on && gl == 0) gw = ldg_f32(gwbase + static_cast<int64_t>(b) * A.ldgw);
       }
       if (seg_end) {
         if constexpr (OPT == DCTR_UPD_LAZY) {

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -39,7 +39,7 @@ class USlot(ctypes.Structure):
     """``dctr_uslot_t`` (include/dctr.h): one X column feeding one general update unit -- 48 bytes."""
     _fields_ = [("col", ctypes.c_int32), ("goff", ctypes.c_int32), ("wide", ctypes.c_int32), ("pool", ctypes.c_int32),
                 ("t", ctypes.c_int32), ("len", ctypes.c_int32), ("len_col", ctypes.c_int32), ("den", ctypes.c_int32),
-                ("am_deep", ctypes.c_int32), ("am_wide", ctypes.c_int32), ("vu0", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+                ("am_deep", ctypes.c_int32), ("am_wide", ctypes.c_int32), ("vu0", ctypes.c_int32), ("wfield", ctypes.c_int32)]
 
 
 class VUnit(ctypes.Structure):
@@ -91,7 +91,8 @@ class DenseItem(ctypes.Structure):
                 ("l2", ctypes.c_float), ("pad_", ctypes.c_float)]
 
 
-PLAN_HAS_GACC, PLAN_HAS_STATE, PLAN_HAS_MAXPOOL = 1, 2, 4
+PLAN_HAS_GACC, PLAN_HAS_STATE, PLAN_HAS_MAXPOOL, PLAN_WIDE_PER_FIELD = 1, 2, 4, 8
+IAFM_SOFTMAX, IAFM_SUM = 0, 1
 LAZY_SGD, LAZY_ADAGRAD, LAZY_ADAM, LAZY_RMSPROP = 0, 1, 2, 3
 
 
@@ -228,6 +229,11 @@ SIGNATURES = {
                                                     _P, _I64, _P, _I64, _P, _I32, _P, _P, _I64, _P, _P]),
     "dctr_fm_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "dctr_fm_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _I64, _I32, _P]),
+    "dctr_iafm_supported": (ctypes.c_int, [_I32, _I32]),
+    "dctr_iafm_fwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P,
+                                     _P]),
+    "dctr_iafm_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _I64,
+                                     _P, _I64, _P]),
     "dctr_interacting_supported": (ctypes.c_int, [_I32, _I32, _I32]),
     "dctr_interacting_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32]),
     "dctr_interacting_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),

@@ -58,7 +58,9 @@ class EmbedFunction(torch.autograd.Function):
         B = X.shape[0]
         cplan = plan.bind(X.device)
         out = torch.empty((B, plan.ld_out), dtype=torch.float32, device=X.device) if plan.has_lookup else None
-        wide = torch.empty((B,), dtype=torch.float32, device=X.device) if plan.has_wide else None
+        # (a per-field-wide plan: [B, ld_wide] -- column f = wide field f, the last column the dense half of Linear)
+        wide = torch.empty((B, plan.ld_wide) if plan.wide_per_field else (B,), dtype=torch.float32,
+                           device=X.device) if plan.has_wide else None
         fm = torch.empty((B,), dtype=torch.float32, device=X.device) if want_fm else None
         if want_fm and (plan.emb_dim <= 0 or not plan.deep):
             raise ValueError("FM needs sparse features that share one embedding_dim")
@@ -96,7 +98,7 @@ class EmbedFunction(torch.autograd.Function):
 
         def gather(stream, with_ids):
             fused_ids = with_ids and plan.gen is None      # (a general unit spans several X columns: dctr_embed_ids)
-            L.check(lib.dctr_embed_fwd(cplan, _ptr(X), X.stride(0), B, _ptr(out), plan.ld_out, _ptr(wide), 1,
+            L.check(lib.dctr_embed_fwd(cplan, _ptr(X), X.stride(0), B, _ptr(out), plan.ld_out, _ptr(wide), plan.ld_wide,
                                        _ptr(fm), _ptr(err), plan.units_ptr(), plan.n_grid_units,
                                        _ptr(ids_t) if fused_ids else None, _ptr(parts_t) if fused_ids else None,
                                        _ptr(fm_s), ld_s, stream), "dctr_embed_fwd")
@@ -115,7 +117,7 @@ class EmbedFunction(torch.autograd.Function):
         ctx.save_for_backward(X, out if (want_fm or plan.gen is not None) else None, ids_t, fm_s, parts_t, den_t, amax)
         ctx.set_materialize_grads(False)
         outs = (out if out is not None else X.new_zeros((B, 0)),
-                wide if wide is not None else X.new_zeros((B,)),
+                wide if wide is not None else X.new_zeros((B, plan.ld_wide) if plan.wide_per_field else (B,)),
                 fm if fm is not None else X.new_zeros((B,)))
         return outs
 
@@ -146,7 +148,8 @@ class EmbedFunction(torch.autograd.Function):
                         g_wd = torch.empty((len(plan.wdense_cols), 1), dtype=torch.float32, device=X.device)
                         g_w = g_wd
                 else:
-                    g_w = plan.dense_matrix(X, plan.wdense_cols).t().mv(g_wide).unsqueeze(1)
+                    g_dense = g_wide[:, len(plan.wide)] if plan.wide_per_field else g_wide
+                    g_w = plan.dense_matrix(X, plan.wdense_cols).t().mv(g_dense).unsqueeze(1)
         if g_fm is not None:
             g_fm = g_fm.contiguous()
         ld_g = 0
@@ -180,8 +183,8 @@ class EmbedFunction(torch.autograd.Function):
                 return None, None, None, g_w, None, None
             L.check(lib.dctr_embed_update(cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, _ptr(ids_t),
                                           _ptr(parts_t), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out, _ptr(fm_s),
-                                          fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide), 1,
-                                          L.UPD_ACCUM, 0.0, 0.0, _ptr(X), X.stride(0), _ptr(g_wd), None, _ptr(ws), ws_n,
+                                          fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide),
+                                          plan.ld_wide, L.UPD_ACCUM, 0.0, 0.0, _ptr(X), X.stride(0), _ptr(g_wd), None, _ptr(ws), ws_n,
                                           pre, stream), "dctr_embed_update(accumulate)")
             lazy.apply(ids_t)
             return None, None, None, g_w, None, None
@@ -216,8 +219,8 @@ class EmbedFunction(torch.autograd.Function):
                 wd = ctypes.byref(inline) if (inline is not None and g_wd is not None and g_w is None) else None
                 L.check(lib.dctr_embed_update(cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, _ptr(ids_t),
                                               _ptr(parts_t), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out, _ptr(fm_s),
-                                              fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide), 1,
-                                              opt, lr, eps, _ptr(X), X.stride(0), _ptr(g_wd), wd, _ptr(ws), ws_n, pre,
+                                              fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide),
+                                              plan.ld_wide, opt, lr, eps, _ptr(X), X.stride(0), _ptr(g_wd), wd, _ptr(ws), ws_n, pre,
                                               L.stream_handle(X.device)), "dctr_embed_update")
             if side is not None:
                 # (everything the side-stream kernels touch stays allocated until the join)
@@ -505,6 +508,81 @@ class BiPoolFunction(torch.autograd.Function):
         L.check(lib.dctr_bi_pooling_bwd(_ptr(G), G.stride(0), B, F, D, dense_off, n_dense, _ptr(gout), gout.stride(0),
                                         _ptr(gG), gG.stride(0), L.stream_handle(G.device)), "dctr_bi_pooling_bwd")
         return gG, None, None, None, None
+
+
+# ---- input-aware FM of IFM / DIFM (ifm.py:74-83, difm.py:96-102, basemodel.py:80-91; csrc/iafm.hip) -----------------
+class IAFMFunction(torch.autograd.Function):
+    """``(G, Wl | None, Z1, Z2 | None) -> (y_lin [B, 1], y_fm [B, 1])`` with ``m = F softmax(Z1)`` or ``Z1 + Z2``:
+    the refined wide sum and FM on the refined embeddings, one launch per direction.  ``G [B, ld]`` is the gather's buffer
+    (its first ``F * D`` columns are read in place; the gradient handed back has G's layout, zero outside the field block),
+    ``Wl [B, n_wl + 1]`` the per-field wide buffer of a ``wide_per_field`` plan (its gradient is that plan's ``g_wide``)."""
+
+    @staticmethod
+    def forward(ctx, G, Wl, Z1, Z2, mode, F, D, n_wl):
+        lib = L.lib()
+        L.require_gpu(G, "input-aware FM input")
+        if G.dtype != torch.float32 or G.dim() != 2 or G.stride(1) != 1:
+            G = G.float().contiguous()
+        Z1 = _rows_f32(Z1, "input-aware factor")
+        Z2 = _rows_f32(Z2, "input-aware factor") if Z2 is not None else None
+        Wl = _rows_f32(Wl, "per-field wide weights") if Wl is not None else None
+        B = G.shape[0]
+        dev = G.device
+        m = torch.empty((B, F), dtype=torch.float32, device=dev)
+        y_lin = torch.empty((B,), dtype=torch.float32, device=dev)
+        y_fm = torch.empty((B,), dtype=torch.float32, device=dev)
+        L.check(lib.dctr_iafm_fwd(_ptr(G), G.stride(0), _ptr(Wl), Wl.stride(0) if Wl is not None else 0, n_wl, _ptr(Z1),
+                                  Z1.stride(0), _ptr(Z2), Z2.stride(0) if Z2 is not None else 0, mode, B, F, D, _ptr(m), F,
+                                  _ptr(y_lin), _ptr(y_fm), L.stream_handle(dev)), "dctr_iafm_fwd")
+        ctx.save_for_backward(G, Wl, m)
+        ctx.cfg = (int(mode), int(F), int(D), int(n_wl), Z2 is not None)
+        ctx.set_materialize_grads(False)
+        return y_lin.unsqueeze(1), y_fm.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, g_lin, g_fm):
+        lib = L.lib()
+        G, Wl, m = ctx.saved_tensors
+        mode, F, D, n_wl, two = ctx.cfg
+        if g_lin is None and g_fm is None:
+            return None, None, None, None, None, None, None, None
+        B = G.shape[0]
+        dev = G.device
+        g_lin = g_lin.reshape(B).contiguous().float() if g_lin is not None else None
+        g_fm = g_fm.reshape(B).contiguous().float() if g_fm is not None else None
+        gG = torch.empty_like(G)
+        if G.shape[1] > F * D:
+            gG[:, F * D:].zero_()      # (the kernel writes the field block only; autograd adds the tower's gradient to this)
+        gWl = torch.empty_like(Wl) if Wl is not None else None
+        gZ = torch.empty((B, F), dtype=torch.float32, device=dev)
+        L.check(lib.dctr_iafm_bwd(_ptr(G), G.stride(0), _ptr(Wl), Wl.stride(0) if Wl is not None else 0, n_wl, _ptr(m), F,
+                                  mode, B, F, D, _ptr(g_lin), _ptr(g_fm), _ptr(gG), gG.stride(0), _ptr(gWl),
+                                  gWl.stride(0) if gWl is not None else 0, _ptr(gZ), F, L.stream_handle(dev)),
+                "dctr_iafm_bwd")
+        return gG, gWl, gZ, (gZ if two else None), None, None, None, None
+
+
+def iafm_supported(F, D):
+    return bool(L.lib().dctr_iafm_supported(int(F), int(D)))
+
+
+def iafm(G, Wl, Z1, Z2, softmax, F, D):
+    """``(y_lin [B, 1], y_fm [B, 1])`` of the input-aware FM over the gather's buffer ``G`` (see IAFMFunction).  ``Wl`` is the
+    per-field wide buffer ``[B, n + 1]`` (n = F, or 0 for a linear side of dense columns only) or None (no linear side).
+    Shapes the kernel does not hold (``dctr_iafm_supported``) take the same formulas as torch ops."""
+    n_wl = 0 if Wl is None else int(Wl.shape[1]) - 1
+    if iafm_supported(F, D):
+        return IAFMFunction.apply(G, Wl, Z1, Z2, L.IAFM_SOFTMAX if softmax else L.IAFM_SUM, int(F), int(D), n_wl)
+    B = G.shape[0]
+    m = float(F) * Z1.softmax(1) if softmax else Z1 + Z2
+    y_lin = torch.zeros((B, 1), dtype=G.dtype, device=G.device)
+    if Wl is not None:
+        if n_wl:
+            y_lin = y_lin + torch.sum(Wl[:, :n_wl] * m, dim=1, keepdim=True)
+        y_lin = y_lin + Wl[:, n_wl:n_wl + 1]
+    v = G[:, :F * D].reshape(B, F, D) * m.unsqueeze(-1)
+    y_fm = 0.5 * torch.sum(torch.pow(torch.sum(v, dim=1), 2) - torch.sum(v * v, dim=1), dim=1, keepdim=True)
+    return y_lin, y_fm
 
 
 # ---- CIN layer (interaction.py:207-248) ----------------------------------------------------------------

@@ -301,7 +301,7 @@ class LazyState(object):
         P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())       # noqa: E731
         rc = L.lib().dctr_embed_update_lazy(
             cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, P(ids_t), P(parts_t), B, P(g_out), ld_g, P(out),
-            plan.ld_out, P(fm_s), fm_s.stride(0) if fm_s is not None else 0, P(g_fm), P(g_wide), 1, P(X), X.stride(0), P(g_wd),
+            plan.ld_out, P(fm_s), fm_s.stride(0) if fm_s is not None else 0, P(g_fm), P(g_wide), plan.ld_wide, P(X), X.stride(0), P(g_wd),
             P(ws), ws_n, ctypes.c_void_p(self._units_dev.data_ptr()), ctypes.c_void_p(self.step.data_ptr()),
             ctypes.byref(self.opt), L.stream_handle(X.device))
         if rc == L.ENOSUP:
@@ -359,11 +359,16 @@ class EmbeddingPlan(object):
 
     deep side  = ``dnn_feature_columns`` over ``embedding_dict``          (basemodel.py:354-380)
     wide side  = ``linear_feature_columns`` over ``Linear.embedding_dict`` (basemodel.py:63-92)
+
+    ``wide_per_field``: the gather hands the first-order weights out PER FIELD instead of summed (``wide [B, ld_wide]``:
+    column f = wide field f, column ``n_wide`` = the dense half of Linear) and the update reads their gradient in the
+    same layout (DCTR_PLAN_WIDE_PER_FIELD, include/dctr.h) -- IFM / DIFM re-weight them per sample before the sum.
     """
 
     def __init__(self, feature_index, deep_columns=(), deep_tables=None, wide_columns=(), wide_tables=None,
-                 wide_dense_weight=None, unpooled=False, with_dense=True):
+                 wide_dense_weight=None, unpooled=False, with_dense=True, wide_per_field=False):
         self.feature_index = feature_index
+        self.wide_per_field = bool(wide_per_field)
         self.n_xcols = max([hi for (_, hi) in feature_index.values()] + [1])
         dfix, dpool, emb_width = _fields_for(deep_columns, deep_tables, feature_index, unpooled) \
             if deep_tables is not None else ([], [], 0)
@@ -372,6 +377,7 @@ class EmbeddingPlan(object):
         self.deep = dfix + dpool
         self.wide = wfix + wpool
         self.n_deep_fixed, self.n_wide_fixed = len(dfix), len(wfix)
+        self.ld_wide = len(self.wide) + 1 if self.wide_per_field else 1      # floats per sample of `wide` / `g_wide`
         self.emb_width = emb_width
         dims = sorted(set(f.dim for f in self.deep))
         self.emb_dim = dims[0] if len(dims) == 1 else 0
@@ -499,7 +505,7 @@ class EmbeddingPlan(object):
                 slots.append(dict(col=col, goff=self.deep[fdi].out_off if fdi >= 0 else -1, wide=1 if fwi >= 0 else 0,
                                   pool=pool, t=t, len=length, len_col=len_col, den=den,
                                   am_deep=am_deep[fdi] if fdi >= 0 else -1, am_wide=am_wide[fwi] if fwi >= 0 else -1,
-                                  vu0=vu0))
+                                  vu0=vu0, wfield=fwi))
             k = ns                      # groups of P partitions: a partition then holds ~96 entries whatever the slots
             kshift = 32 + max(0, (k - 1).bit_length())
             for j in range(k):
@@ -571,6 +577,8 @@ class EmbeddingPlan(object):
 
     def __setstate__(self, d):
         self.__dict__.update(d)
+        self.__dict__.setdefault("wide_per_field", False)      # (a plan pickled before the mode existed)
+        self.__dict__.setdefault("ld_wide", 1)
         self._reset_device_image()
 
     # ---- sparse-update mode (see ops.py) ---------------------------------------------------------
@@ -735,6 +743,8 @@ class EmbeddingPlan(object):
             flags |= L.PLAN_HAS_STATE
         if self.has_maxpool:
             flags |= L.PLAN_HAS_MAXPOOL
+        if self.wide_per_field:
+            flags |= L.PLAN_WIDE_PER_FIELD
         c.flags = flags
         c.ext = None
         if self.gen is not None:

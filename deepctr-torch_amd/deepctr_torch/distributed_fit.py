@@ -197,6 +197,8 @@ class _Unsharded(object):
 
 def fit(model, X_all, y_all, batch_size, epochs, verbose, initial_epoch, do_validation, val_x, val_y, shuffle, callbacks):
     from . import callbacks as _cb
+    from .parallel import _refuse_wide_per_field
+    _refuse_wide_per_field(model.model_plan(), "fit() under torchrun")
     dist = _ensure_group(model.device)
     world, rank = dist.get_world_size(), dist.get_rank()
     dev = X_all.device

@@ -6,10 +6,13 @@ from .basemodel import BaseModel, Linear
 from .dcn import DCN
 from .dcnmix import DCNMix
 from .deepfm import DeepFM
+from .difm import DIFM
 from .fibinet import FiBiNET
+from .ifm import IFM
 from .nfm import NFM
 from .pnn import PNN
 from .wdl import WDL
 from .xdeepfm import xDeepFM
 
-__all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix"]
+__all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
+           "IFM", "DIFM"]

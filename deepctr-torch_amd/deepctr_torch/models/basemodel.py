@@ -113,6 +113,9 @@ class Linear(nn.Module):
 
 
 class BaseModel(nn.Module):
+    # IFM / DIFM: the model plan hands the first-order weights out per field (EmbeddingPlan(wide_per_field=True))
+    _wide_per_field = False
+
     def __init__(self, linear_feature_columns, dnn_feature_columns, l2_reg_linear=1e-5, l2_reg_embedding=1e-5,
                  init_std=0.0001, seed=1024, task='binary', device='cpu', gpus=None):
         super(BaseModel, self).__init__()
@@ -203,7 +206,8 @@ class BaseModel(nn.Module):
             self._plan = EmbeddingPlan(self.feature_index, deep_columns=self.dnn_feature_columns,
                                        deep_tables=self.embedding_dict,
                                        wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
-                                       wide_dense_weight=getattr(lm, "weight", None))
+                                       wide_dense_weight=getattr(lm, "weight", None),
+                                       wide_per_field=self._wide_per_field)
             object.__setattr__(self.embedding_dict, "_dctr_owner_plan", self._plan)
             object.__setattr__(lm.embedding_dict, "_dctr_owner_plan", self._plan)
             if lm._plan is not None:

@@ -113,6 +113,14 @@ def fold_fm(g_out, width, out, fm_s, g_fm, emb_dim):
     return G
 
 
+def _refuse_wide_per_field(plan, who):
+    """IFM / DIFM take their first-order weights per field out of the gather (EmbeddingPlan(wide_per_field=True)): the
+    payloads and exchanges of the multi-GPU trainers carry ONE wide gradient per sample."""
+    if getattr(plan, "wide_per_field", False):
+        raise NotImplementedError("%s: this model's plan hands out per-field first-order weights (IFM / DIFM); "
+                                  "multi-GPU training of these models is not implemented -- train on one GPU" % who)
+
+
 class DataParallelTrainer(object):
     """``trainer.train_step(xb, yb)`` == ``model._train_step`` on the concatenation of every rank's batch."""
 
@@ -124,6 +132,7 @@ class DataParallelTrainer(object):
         self.world = dist.get_world_size(process_group)
         self.rank = dist.get_rank(process_group)
         self.plan = model.model_plan()
+        _refuse_wide_per_field(self.plan, "DataParallelTrainer")
         self._forced_dense = False
         # The lazy regularised / Adam table update (the reference's DEFAULT kwargs: L2 on every table, adam) stays lazy on
         # replicated tables (round 6): a row's replayed steps are a function of (row, step) alone, so every replica that
@@ -919,6 +928,7 @@ class ShardedTrainer(object):
         self.model, self.group = model, process_group
         self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         self.plan = model.model_plan()
+        _refuse_wide_per_field(self.plan, "ShardedTrainer")
         if broadcast_parameters:
             with torch.no_grad():
                 for p in model.parameters():

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 26
+#define DCTR_ABI_VERSION 27
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -86,7 +86,7 @@ typedef struct dctr_uslot {
   int32_t am_deep;  /* byte offset in an amax row of the deep field's per-element arg-max positions (max pooling); -1 */
   int32_t am_wide;  /* the same for the wide field (one byte); -1                                                    */
   int32_t vu0;      /* first vunit of the slot's unit                                                                */
-  int32_t pad_;
+  int32_t wfield;   /* index of the slot's wide field (its column of a per-field g_wide, DCTR_PLAN_WIDE_PER_FIELD); -1   */
 } dctr_uslot_t;
 
 typedef struct dctr_vunit {
@@ -156,6 +156,14 @@ typedef struct dctr_plan {
 #define DCTR_PLAN_HAS_GACC 1    /* every field has a gacc slab                       */
 #define DCTR_PLAN_HAS_STATE 2   /* every field has an optimizer state slab           */
 #define DCTR_PLAN_HAS_MAXPOOL 4 /* some VarLen field uses DCTR_POOL_MAX              */
+/* The first-order weights PER FIELD instead of summed (IFM / DIFM re-weight them per sample before the sum,
+ * basemodel.py:80-91).  dctr_embed_fwd then writes wide[b * ld_wide + f] = w_f[id] for f < n_wide (a VarLen wide field
+ * pooled as always) and the dense half of Linear, sum_j X[b, wdense_cols[j]] * wdense_w[j], into column n_wide
+ * (ld_wide >= n_wide + 1); dctr_embed_update / dctr_embed_update_lazy read the gradient of wide field f at
+ * g_wide[b * ld_gw + f] and that of the dense half (for g_wdense) at column n_wide; dctr_embed_bwd, which has no ld_gw,
+ * takes g_wide as dense rows of n_wide + 1 floats.  Entry points that cannot honour the bit refuse it:
+ * dctr_embed_tower_train_supported returns 0, plan->out_chunks and the shard kernels' callers get DCTR_ENOSUP.       */
+#define DCTR_PLAN_WIDE_PER_FIELD 8
 
 int dctr_abi_version(void);
 const char* dctr_strerror(int code);
@@ -303,6 +311,32 @@ int dctr_fm_fwd(const float* E, int64_t ld_b, int32_t B, int32_t F, int32_t D, f
                 dctr_stream_t stream);
 int dctr_fm_bwd(const float* E, int64_t ld_b, int32_t B, int32_t F, int32_t D, const float* gy,
                 float* gE, int64_t ld_gb, int32_t accumulate, dctr_stream_t stream);
+
+/* ---- input-aware FM of IFM / DIFM (ifm.py:74-83, difm.py:96-102, basemodel.py:80-91; csrc/iafm.hip) -------------
+ * One launch per direction for the reference's softmax, two broadcasts, concat, FM and refined wide sum:
+ *   m      = F * softmax_f(Z1)   DCTR_IAFM_SOFTMAX (stable: the row maximum is subtracted)   |   Z1 + Z2   DCTR_IAFM_SUM
+ *   y_lin  = sum_f m_f * wl_f + wl_dense
+ *   y_fm   = 0.5 * sum_d ((sum_f m_f e_fd)^2 - sum_f (m_f e_fd)^2)
+ *   E  [B, F, D] rows at E + b*ld_e: the gather's buffer read in place (ld_e >= F*D)
+ *   Wl [B, ld_w] the per-field wide buffer of a DCTR_PLAN_WIDE_PER_FIELD plan: columns 0 .. n_wl-1 are wl_f, column
+ *      n_wl the dense half; n_wl is F or 0 (then only the dense column counts); Wl = NULL: y_lin = 0
+ *   Z1 / Z2 [B, F] rows ld_z1 / ld_z2 apart (Z2 only in SUM mode);  m [B, F] is written for the backward
+ * backward, with S_d = sum_f m_f e_fd and v_fd = m_f e_fd:
+ *   gE_fd = g_fm m_f (S_d - v_fd);  gm_f = g_lin wl_f + g_fm sum_d e_fd (S_d - v_fd);  gWl_f = g_lin m_f, gWl[n_wl] = g_lin
+ *   gZ = gm (SUM: one buffer serves Z1 and Z2)  |  gZ_k = m_k (gm_k - (1/F) sum_f gm_f m_f) (SOFTMAX)
+ *   gE has E's row layout (columns past F*D are not written), gWl has Wl's (NULL when Wl is).
+ * A group of lanes per sample holds the row in registers (read once), reductions by wave shuffles in a fixed order:
+ * no atomics, identical bits from run to run.  dctr_iafm_supported(F, D) != 0 iff the shape fits (1 <= F <= 64, the row
+ * in 8 strips per lane of a 64-lane group); the entry points return DCTR_ENOSUP otherwise.                          */
+#define DCTR_IAFM_SOFTMAX 0
+#define DCTR_IAFM_SUM 1
+int dctr_iafm_supported(int32_t F, int32_t D);
+int dctr_iafm_fwd(const float* E, int64_t ld_e, const float* Wl, int64_t ld_w, int32_t n_wl, const float* Z1,
+                  int64_t ld_z1, const float* Z2, int64_t ld_z2, int32_t mode, int32_t B, int32_t F, int32_t D, float* m,
+                  int64_t ld_m, float* y_lin, float* y_fm, dctr_stream_t stream);
+int dctr_iafm_bwd(const float* E, int64_t ld_e, const float* Wl, int64_t ld_w, int32_t n_wl, const float* m, int64_t ld_m,
+                  int32_t mode, int32_t B, int32_t F, int32_t D, const float* g_lin, const float* g_fm, float* gE,
+                  int64_t ld_ge, float* gWl, int64_t ld_gw, float* gZ, int64_t ld_gz, dctr_stream_t stream);
 
 /* ---- BiInteractionPooling (interaction.py:54-61) + NFM's combined_dnn_input (nfm.py:66-71) ---------------------
  *   bi[b, d] = 0.5 * ((sum_f e[b,f,d])^2 - sum_f e[b,f,d]^2)           out row b = [ bi (D) | dense (n_dense) ]
