@@ -16,121 +16,11 @@
 //     gather costs about one more HBM round trip;
 //   * FM / wide-logit partials of the 4 waves meet in LDS; the final reduction inside a sample group
 //     uses DPP shuffles.
-#include "common.hpp"
+#include "embed_tile.hpp"
 
 using namespace dctr;
 
 namespace {
-
-constexpr int kNW = 4;  // waves per workgroup
-constexpr int kThreads = kNW * kWave;
-constexpr int kFieldWords = sizeof(dctr_field_t) / 4;
-static_assert(sizeof(dctr_field_t) == 64, "dctr_field_t must be 64 bytes");
-static_assert(sizeof(dctr_plan_t) == 112, "dctr_plan_t layout changed: update the Python binding");
-
-struct Tile {
-  const dctr_field_t* deep;
-  const dctr_field_t* wide;
-  const float* xs;  // [SPB][n_xcols]
-  float* red;       // [kNW][kWave][RED] cross-wave reduction scratch
-};
-
-// Copy descriptors and the X tile of samples [b0, b0+nrows) into LDS (whole workgroup).
-__device__ __forceinline__ Tile stage_tile(const dctr_plan_t& P, const float* __restrict__ X,
-                                           int64_t ldx, int b0, int nrows, int spb,
-                                           unsigned char* smem) {
-  const int tid = threadIdx.x;
-  uint32_t* w = reinterpret_cast<uint32_t*>(smem);
-  const int nd = P.n_deep * kFieldWords, nw = P.n_wide * kFieldWords;
-  const uint32_t* gd = reinterpret_cast<const uint32_t*>(P.deep);
-  const uint32_t* gw = reinterpret_cast<const uint32_t*>(P.wide);
-  for (int i = tid; i < nd; i += kThreads) w[i] = gd[i];
-  for (int i = tid; i < nw; i += kThreads) w[nd + i] = gw[i];
-  float* xs = reinterpret_cast<float*>(w + nd + nw);
-  const int nc = P.n_xcols;
-  const int n = nrows * nc;
-  if (ldx == nc) {
-    const float* src = X + static_cast<int64_t>(b0) * ldx;
-    for (int i = tid; i < n; i += kThreads) xs[i] = src[i];
-  } else {
-    for (int i = tid; i < n; i += kThreads) {
-      const int r = i / nc, c = i - r * nc;
-      xs[i] = X[static_cast<int64_t>(b0 + r) * ldx + c];
-    }
-  }
-  __syncthreads();
-  Tile t;
-  t.deep = reinterpret_cast<const dctr_field_t*>(w);
-  t.wide = reinterpret_cast<const dctr_field_t*>(w + nd);
-  t.xs = xs;
-  t.red = xs + ((spb * nc + 3) & ~3);
-  return t;
-}
-
-// id = Tensor.long() of the float in X: truncation toward zero (basemodel.py:369).  float32 holds
-// integers exactly only below 2^24, so a 32-bit convert (one v_cvt_i32_f32) is exact
-// for every id the reference can represent.
-__device__ __forceinline__ int64_t raw_id(const float* xr, int col) {
-  return static_cast<int64_t>(static_cast<int32_t>(xr[col]));
-}
-
-// Out-of-range ids read row 0 and raise `bad`; the caller ORs it into the error word once.
-__device__ __forceinline__ int64_t checked(int64_t id, int64_t vocab, int& bad) {
-  const bool oob = static_cast<uint64_t>(id) >= static_cast<uint64_t>(vocab);
-  bad |= oob ? 1 : 0;
-  return oob ? 0 : id;
-}
-
-// Pool one VarLen field for this lane's strip of the row.  Mirrors SequencePoolingLayer.forward
-// (sequence.py:49-77) as called from get_varlen_pooling_list (inputs.py:141-155):
-//   mask mode   (len_col < 0): m_t = (id_t != 0); length = sum_t m_t
-//   length mode (len_col >= 0): m_t = (t < length)
-//   sum : sum_t m_t e_t        mean: that / (length + 1e-8)        max: max_t (e_t - (1 - m_t) * 1e9)
-//   am (nullable; max pooling): this sample's arg-max bytes of the field at e0 -- the position of the FIRST maximum per
-//   element (torch.max's backward routes the gradient there), the side output dctr_embed_update reads
-template <int VEC>
-__device__ __forceinline__ Strip<VEC> pool_field(const dctr_field_t& fd, const float* xr, int e0,
-                                                 bool act, int& bad, uint8_t* am = nullptr) {
-  const bool by_len = fd.len_col >= 0;
-  const int64_t len_i = by_len ? raw_id(xr, fd.len_col) : 0;
-  Strip<VEC> acc;
-  int arg[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    acc.v[i] = (fd.pool == DCTR_POOL_MAX) ? -INFINITY : 0.f;
-    arg[i] = 0;
-  }
-  float cnt = 0.f;
-  for (int t = 0; t < fd.len; ++t) {
-    const int64_t rid = raw_id(xr, fd.col + t);
-    const bool m = by_len ? (static_cast<int64_t>(t) < len_i) : (rid != 0);
-    const int64_t id = checked(rid, fd.vocab, bad);
-    Strip<VEC> row = act ? strip_load<VEC>(fd.table + id * row_ld(fd) + e0) : strip_zero<VEC>();
-    if (fd.pool == DCTR_POOL_MAX) {
-      const float pen = m ? 0.f : 1e9f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        const float v = row.v[i] - pen;
-        arg[i] = (v > acc.v[i]) ? t : arg[i];
-        acc.v[i] = (v > acc.v[i]) ? v : acc.v[i];
-      }
-    } else if (m) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc.v[i] += row.v[i];
-    }
-    cnt += m ? 1.f : 0.f;
-  }
-  if (fd.pool == DCTR_POOL_MEAN) {
-    const float den = (by_len ? static_cast<float>(len_i) : cnt) + 1e-8f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc.v[i] = acc.v[i] / den;
-  }
-  if (am && act && fd.pool == DCTR_POOL_MAX) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) *(DCTR_GLOBAL uint8_t*)(am + i) = static_cast<uint8_t>(arg[i]);
-  }
-  return acc;
-}
 
 // -------------------------------------------------------------------------------------------------
 // forward
@@ -154,7 +44,6 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
   step_priority();
   constexpr int SPB = kWave / LPR;
   constexpr int CH = 8;   // row loads in flight per lane and per pass (x4 waves = 32 fields)
-  constexpr int WCH = 2;  // wide loads in flight per lane and per pass
   constexpr int RED = 2 * VEC + 1;
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, wv_id = tid >> 6, lane = tid & 63;
@@ -197,22 +86,11 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
     }
   }
 
-  // ---- wide (1-dim) tables: (wave, lane-in-group) pairs split the fields; loads issued first ----
-  // Branch-free: slots past the last field re-read the last field and are masked when summed, so
-  // each pass is one basic block and the scheduler can overlap every LDS/HBM access.
+  // ---- wide (1-dim) tables: (wave, lane-in-group) pairs split the fields; loads issued first (embed_tile.hpp) ----
   float ws = 0.f;
   const int nwf = wide ? P.n_wide_fixed : 0;
-  float wval[WCH];
-#pragma unroll
-  for (int k = 0; k < WCH; ++k) wval[k] = 0.f;
-  if (nwf > 0) {
-#pragma unroll
-    for (int k = 0; k < WCH; ++k) {
-      const int f = (k * kNW + wv_id) * LPR + gl;
-      const dctr_field_t& fd = T.wide[min(f, nwf - 1)];
-      wval[k] = ldg_f32(fd.table + checked(raw_id(xr, fd.col), fd.vocab, bad) * row_ld(fd));
-    }
-  }
+  float wval[kWideCH];
+  wide_issue<LPR>(T, xr, wv_id, gl, nwf, wval, bad);
 
   // ---- deep fixed-length fields: issue every row load of a pass, then consume -------------------
   Strip<VEC> S = strip_zero<VEC>(), Q = strip_zero<VEC>();
@@ -268,38 +146,9 @@ __global__ __launch_bounds__(kThreads) void k_embed_fwd(dctr_plan_t P, const flo
     }
   }
 
-  if (wide) {
-    if (wpf) {
-#pragma unroll
-      for (int k = 0; k < WCH; ++k) {
-        const int f = (k * kNW + wv_id) * LPR + gl;
-        if (f < nwf && valid) stg_f32(wrow + f, wval[k]);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < WCH; ++k) ws += ((k * kNW + wv_id) * LPR + gl < nwf) ? wval[k] : 0.f;
-    }
-    for (int f = (WCH * kNW + wv_id) * LPR + gl; f < nwf; f += kNW * LPR) {  // > 8*LPR wide fields
-      const dctr_field_t& fd = T.wide[f];
-      const float wv = ldg_f32(fd.table + checked(raw_id(xr, fd.col), fd.vocab, bad) * row_ld(fd));
-      if (!wpf) ws += wv;
-      else if (valid) stg_f32(wrow + f, wv);
-    }
-    for (int f = P.n_wide_fixed + wv_id * LPR + gl; f < P.n_wide; f += kNW * LPR) {  // pooled VarLen
-      const dctr_field_t& fd = T.wide[f];
-      uint8_t* am = nullptr;
-      if (amax && valid && fd.pool == DCTR_POOL_MAX) {
-        const int off = ldg_i32(am_wide_off + f);
-        if (off >= 0) am = amax + static_cast<int64_t>(b) * ld_am + off;
-      }
-      const float wv = pool_field<1>(fd, xr, 0, true, bad, am).v[0];
-      if (!wpf) ws += wv;
-      else if (valid) stg_f32(wrow + f, wv);
-    }
-    if (P.wdense_w)
-      for (int j = wv_id * LPR + gl; j < P.n_wdense; j += kNW * LPR)
-        ws += xr[ldg_i32(P.wdense_cols + j)] * ldg_f32(P.wdense_w + j);
-  }
+  if (wide)
+    ws = wide_finish<LPR>(P, T, xr, wv_id, gl, nwf, wval, valid, wrow,
+                          (amax && valid) ? amax + static_cast<int64_t>(b) * ld_am : nullptr, am_wide_off, bad);
 
   // ---- the 4 waves' partials meet in LDS; wave 0 finishes --------------------------------------
   if (fm || wide || fm_s) {
@@ -565,57 +414,7 @@ __global__ __launch_bounds__(kThreads) void k_embed_apply(dctr_plan_t P, const f
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-int lanes_per_row(const dctr_plan_t* p, int vec) {
-  int need = (p->max_dim + vec - 1) / vec;
-  int lpr = 1;
-  while (lpr < need) lpr <<= 1;
-  return lpr;
-}
-
-size_t tile_bytes(const dctr_plan_t* p, int lpr, int vec) {
-  const size_t spb = kWave / lpr;
-  return static_cast<size_t>(p->n_deep + p->n_wide) * sizeof(dctr_field_t) +
-         ((spb * p->n_xcols + 3) & ~size_t(3)) * sizeof(float) +
-         static_cast<size_t>(kNW) * kWave * (2 * vec + 1) * sizeof(float);
-}
-
-int check_plan(const dctr_plan_t* p, const float* X, int64_t ldx, int32_t B) {
-  if (!p || !X || B < 0 || p->n_xcols <= 0 || ldx < p->n_xcols) return DCTR_EINVAL;
-  if (p->n_deep < 0 || p->n_wide < 0 || p->n_deep_fixed > p->n_deep || p->n_wide_fixed > p->n_wide)
-    return DCTR_EINVAL;
-  if ((p->n_deep && !p->deep) || (p->n_wide && !p->wide)) return DCTR_EINVAL;
-  if (p->vec != 1 && p->vec != 2 && p->vec != 4) return DCTR_EINVAL;
-  if (p->max_dim > 64 * p->vec) return DCTR_ENOSUP;
-  return DCTR_OK;
-}
-
-#define DCTR_DISPATCH_LPR(VEC_, lpr, ...)                                \
-  switch (lpr) {                                                         \
-    case 1: { constexpr int VEC = VEC_, LPR = 1; __VA_ARGS__; } break;   \
-    case 2: { constexpr int VEC = VEC_, LPR = 2; __VA_ARGS__; } break;   \
-    case 4: { constexpr int VEC = VEC_, LPR = 4; __VA_ARGS__; } break;   \
-    case 8: { constexpr int VEC = VEC_, LPR = 8; __VA_ARGS__; } break;   \
-    case 16: { constexpr int VEC = VEC_, LPR = 16; __VA_ARGS__; } break; \
-    case 32: { constexpr int VEC = VEC_, LPR = 32; __VA_ARGS__; } break; \
-    default: { constexpr int VEC = VEC_, LPR = 64; __VA_ARGS__; } break; \
-  }
-
-// Dynamic LDS above the 64 KB default needs the kernel's attribute raised first (gfx950: 160 KB per workgroup).  The
-// tile of a plan with very many input columns (hundreds of VarLen positions, thousands of fields) goes up to kMaxTile.
-constexpr size_t kMaxTile = 156 * 1024;
-#define DCTR_LAUNCH(kernel, grid, block, lds, stream, ...)                                                       \
-  do {                                                                                                           \
-    auto kfn_ = kernel;                                                                                          \
-    if ((lds) > 64 * 1024)                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn_), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                static_cast<int>(lds));                                                          \
-    kfn_<<<grid, block, lds, stream>>>(__VA_ARGS__);                                                             \
-  } while (0)
-
-#define DCTR_DISPATCH(vec, lpr, ...)                              \
-  if ((vec) == 4) { DCTR_DISPATCH_LPR(4, lpr, __VA_ARGS__) }      \
-  else if ((vec) == 2) { DCTR_DISPATCH_LPR(2, lpr, __VA_ARGS__) } \
-  else { DCTR_DISPATCH_LPR(1, lpr, __VA_ARGS__) }
+size_t tile_bytes(const dctr_plan_t* p, int lpr, int vec) { return tile_bytes_red(p, lpr, 2 * vec + 1); }
 
 }  // namespace
 

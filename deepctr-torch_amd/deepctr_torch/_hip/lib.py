@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -133,6 +133,8 @@ SIGNATURES = {
     "dctr_sizeof_plan_ext": (ctypes.c_size_t, []),
     "dctr_embed_fwd": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _P, _I32, _P,
                                       _P, _P, _I64, _P]),
+    "dctr_pair_embed_fwd": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I64, _I32, _P, _I64, _P, _I64, _P, _P]),
+    "dctr_pair_embed_bwd": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I64, _I32, _P, _I64, _P, _I64, _P]),
     "dctr_embed_update_supported": (ctypes.c_int, [ctypes.POINTER(Plan), _I64, _I32]),
     "dctr_embed_update_partitions": (ctypes.c_int32, [ctypes.POINTER(Plan), _I32]),
     "dctr_embed_ids": (ctypes.c_int, [ctypes.POINTER(Plan), _P, _I32, _P, _I64, _I32, _P, _P, _P]),

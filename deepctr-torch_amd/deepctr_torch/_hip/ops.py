@@ -123,33 +123,16 @@ class EmbedFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_wide, g_fm):
-        lib = L.lib()
         plan = ctx.plan
         X, out, ids_t, fm_s, parts_t, den_t, amax = ctx.saved_tensors
-        B = X.shape[0]
         plan.point_step_buffers(den_t, amax)
-        g_wd = None
         if not plan.has_lookup:
             g_out = None
         if not plan.has_wide:
             g_wide = None
         if not ctx.want_fm:
             g_fm = None
-        g_w = None
-        if g_wide is not None:
-            g_wide = g_wide.contiguous()
-            if plan.wide_dense_weight is not None and ctx.needs_input_grad[3]:
-                # d wide / d Linear.weight = X_dense^T g  (basemodel.py:88-90): an extra workgroup of the
-                # deterministic update kernel when that runs, else a GEMV
-                if ids_t is not None and getattr(plan, "exchange", None) is None and plan.table_params:
-                    sink = getattr(plan, "dense_sink", None)
-                    g_wd = sink.grad_of(plan.wide_dense_weight) if sink is not None else None
-                    if g_wd is None:
-                        g_wd = torch.empty((len(plan.wdense_cols), 1), dtype=torch.float32, device=X.device)
-                        g_w = g_wd
-                else:
-                    g_dense = g_wide[:, len(plan.wide)] if plan.wide_per_field else g_wide
-                    g_w = plan.dense_matrix(X, plan.wdense_cols).t().mv(g_dense).unsqueeze(1)
+        g_wide, g_wd, g_w = _wide_dense_grad(plan, X, g_wide, ids_t, ctx.needs_input_grad[3])
         if g_fm is not None:
             g_fm = g_fm.contiguous()
         ld_g = 0
@@ -157,99 +140,133 @@ class EmbedFunction(torch.autograd.Function):
             g_out, ld_g = _aligned_rows(g_out, plan.vec, 0)
         if (g_out is None and g_fm is None and g_wide is None) or not plan.table_params:
             return None, None, None, g_w, None, None
+        _update_tables(plan, X, ids_t, parts_t, ctx.seg_event, g_out, ld_g, out, fm_s, g_fm, g_wide, g_wd, g_w, den_t, amax)
+        return None, None, None, g_w, None, None
 
-        if getattr(plan, "exchange", None) is not None:
-            # data-parallel: the trainer all-gathers the row gradients and applies the global update
-            plan.exchange(X=X, g_out=g_out, out=out, fm_s=fm_s, g_fm=g_fm, g_wide=g_wide, amax=amax)
-            return None, None, None, g_w, None, None
 
-        update = plan.update
-        kind = update[0]
-        stream = L.stream_handle(X.device)
+def _wide_dense_grad(plan, X, g_wide, ids_t, need_w):
+    """The ``Linear.weight`` side of a lookup's backward: ``(g_wide contiguous | None, g_wd, g_w)`` -- ``g_wd`` is the buffer
+    the deterministic update kernel writes the gradient into (None: it does not), ``g_w`` what autograd gets."""
+    g_wd = None
+    g_w = None
+    if g_wide is not None:
+        g_wide = g_wide.contiguous()
+        if plan.wide_dense_weight is not None and need_w:
+            # d wide / d Linear.weight = X_dense^T g  (basemodel.py:88-90): an extra workgroup of the
+            # deterministic update kernel when that runs, else a GEMV
+            if ids_t is not None and getattr(plan, "exchange", None) is None and plan.table_params:
+                sink = getattr(plan, "dense_sink", None)
+                g_wd = sink.grad_of(plan.wide_dense_weight) if sink is not None else None
+                if g_wd is None:
+                    g_wd = torch.empty((len(plan.wdense_cols), 1), dtype=torch.float32, device=X.device)
+                    g_w = g_wd
+            else:
+                g_dense = g_wide[:, len(plan.wide)] if plan.wide_per_field else g_wide
+                g_w = plan.dense_matrix(X, plan.wdense_cols).t().mv(g_dense).unsqueeze(1)
+    return g_wide, g_wd, g_w
 
-        if kind == "lazy":
-            lazy = plan.lazy
-            if lazy is None or lazy.plan is not plan or ids_t is None:
-                raise NotImplementedError("the lazy regularised / Adam table update needs lookups through the model's "
-                                          "own plan and a batch the deterministic update kernel supports "
-                                          "(DCTR_LAZY_UPDATE=0 selects the exact dense path)")
-            lazy._ensure(X.device)
-            cplan = plan.bind(X.device)
-            ws, ws_n, pre = plan.update_workspace_for(ids_t, ctx.seg_event, B)
-            # round 6: with pre-sorted entries the regularised / Adam step runs at the row, inside the sorted update (no
-            # gradient slab, no second pass over the batch's rows: csrc/update_kernels.hpp DCTR_UPD_LAZY)
-            if pre and lazy.update_fused(plan, cplan, ids_t, parts_t, B, g_out, ld_g, out, fm_s, g_fm, g_wide, X, g_wd, ws,
-                                         ws_n):
-                return None, None, None, g_w, None, None
+
+def _update_tables(plan, X, ids_t, parts_t, seg_event, g_out, ld_g, out, fm_s, g_fm, g_wide, g_wd, g_w, den_t, amax):
+    """What a lookup's backward does with the row gradients, selected by ``plan.update`` (module docstring): hand them to
+    the data-parallel exchange, the lazy regularised / Adam step (fused into the sorted update, or two passes), the
+    deterministic sorted update with the optimizer fused in (sgd / adagrad / dense-accumulate), or the atomic scatter
+    (+ consume pass).  ``g_out [B, ld_g]`` holds field f's gradient at ``plan.deep[f].out_off`` (EmbedFunction: the
+    gradient of its output rows; PairEmbedFunction: the row gradients its backward kernel wrote).  ``ids_t`` /
+    ``parts_t`` / ``seg_event`` / ``den_t`` / ``amax`` are the forward's side outputs (None: the batch is outside what the
+    sorted update takes)."""
+    lib = L.lib()
+    B = X.shape[0]
+    if getattr(plan, "exchange", None) is not None:
+        # data-parallel: the trainer all-gathers the row gradients and applies the global update
+        plan.exchange(X=X, g_out=g_out, out=out, fm_s=fm_s, g_fm=g_fm, g_wide=g_wide, amax=amax)
+        return
+
+    update = plan.update
+    kind = update[0]
+    stream = L.stream_handle(X.device)
+
+    if kind == "lazy":
+        lazy = plan.lazy
+        if lazy is None or lazy.plan is not plan or ids_t is None:
+            raise NotImplementedError("the lazy regularised / Adam table update needs lookups through the model's "
+                                      "own plan and a batch the deterministic update kernel supports "
+                                      "(DCTR_LAZY_UPDATE=0 selects the exact dense path)")
+        lazy._ensure(X.device)
+        cplan = plan.bind(X.device)
+        ws, ws_n, pre = plan.update_workspace_for(ids_t, seg_event, B)
+        # round 6: with pre-sorted entries the regularised / Adam step runs at the row, inside the sorted update (no
+        # gradient slab, no second pass over the batch's rows: csrc/update_kernels.hpp DCTR_UPD_LAZY)
+        if pre and lazy.update_fused(plan, cplan, ids_t, parts_t, B, g_out, ld_g, out, fm_s, g_fm, g_wide, X, g_wd, ws,
+                                     ws_n):
+            return
+        L.check(lib.dctr_embed_update(cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, _ptr(ids_t),
+                                      _ptr(parts_t), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out, _ptr(fm_s),
+                                      fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide),
+                                      plan.ld_wide, L.UPD_ACCUM, 0.0, 0.0, _ptr(X), X.stride(0), _ptr(g_wd), None, _ptr(ws), ws_n,
+                                      pre, stream), "dctr_embed_update(accumulate)")
+        lazy.apply(ids_t)
+        return
+
+    if ids_t is not None:
+        # deterministic single-pass path (csrc/update.hip): no atomics, optimizer fused in
+        if kind == "dense":
+            plan.ensure_gacc()
+            plan.prepare_dense_grads()
+            opt, lr, eps = L.UPD_ACCUM, 0.0, 0.0
+        elif kind in ("sgd", "sgd2"):
+            opt, lr, eps = L.UPD_SGD, float(update[1]), 0.0
+        elif kind == "adagrad":
+            opt, lr, eps = L.UPD_ADAGRAD, float(update[1]), float(update[2])
+        else:
+            raise RuntimeError("unknown sparse update mode %r" % (kind,))
+        cplan = plan.bind(X.device)
+        sink = getattr(plan, "dense_sink", None)
+        # (armed AND carried out by the tower + head kernel of this step: only then has its event been recorded and
+        # does nobody else step Linear.weight)
+        inline = getattr(sink, "inline", None) if (sink is not None and getattr(sink, "inline_done", False)) else None
+        side = None
+        if inline is not None and X.is_cuda and seg_event is not None and seg_event[0] is not True and \
+                sink.update_stream is seg_event[0]:
+            # fused train step with in-kernel optimizer: the update leaves the critical chain -- it runs on the
+            # pre-pass's side stream, behind the pre-pass and behind the tower kernel that produced its gradients,
+            # beside the tower's weight-gradient kernels (which stay on the main stream).  DenseSlab.join() brings
+            # the streams together at the end of the step.
+            side = seg_event[0]      # (already waiting for the tower + head launch: mlp.TowerHeadFunction)
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            ws, ws_n, pre = plan.update_workspace_for(ids_t, seg_event, B)
+            wd = ctypes.byref(inline) if (inline is not None and g_wd is not None and g_w is None) else None
             L.check(lib.dctr_embed_update(cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, _ptr(ids_t),
                                           _ptr(parts_t), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out, _ptr(fm_s),
                                           fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide),
-                                          plan.ld_wide, L.UPD_ACCUM, 0.0, 0.0, _ptr(X), X.stride(0), _ptr(g_wd), None, _ptr(ws), ws_n,
-                                          pre, stream), "dctr_embed_update(accumulate)")
-            lazy.apply(ids_t)
-            return None, None, None, g_w, None, None
+                                          plan.ld_wide, opt, lr, eps, _ptr(X), X.stride(0), _ptr(g_wd), wd, _ptr(ws), ws_n, pre,
+                                          L.stream_handle(X.device)), "dctr_embed_update")
+        if side is not None:
+            # (everything the side-stream kernels touch stays allocated until the join)
+            sink.forked(side, (X, out, ids_t, parts_t, fm_s, g_out, g_fm, g_wide, g_wd, ws, den_t, amax))
+        return
 
-        if ids_t is not None:
-            # deterministic single-pass path (csrc/update.hip): no atomics, optimizer fused in
-            if kind == "dense":
-                plan.ensure_gacc()
-                plan.prepare_dense_grads()
-                opt, lr, eps = L.UPD_ACCUM, 0.0, 0.0
-            elif kind in ("sgd", "sgd2"):
-                opt, lr, eps = L.UPD_SGD, float(update[1]), 0.0
-            elif kind == "adagrad":
-                opt, lr, eps = L.UPD_ADAGRAD, float(update[1]), float(update[2])
-            else:
-                raise RuntimeError("unknown sparse update mode %r" % (kind,))
-            cplan = plan.bind(X.device)
-            sink = getattr(plan, "dense_sink", None)
-            # (armed AND carried out by the tower + head kernel of this step: only then has its event been recorded and
-            # does nobody else step Linear.weight)
-            inline = getattr(sink, "inline", None) if (sink is not None and getattr(sink, "inline_done", False)) else None
-            side = None
-            if inline is not None and X.is_cuda and ctx.seg_event is not None and ctx.seg_event[0] is not True and \
-                    sink.update_stream is ctx.seg_event[0]:
-                # fused train step with in-kernel optimizer: the update leaves the critical chain -- it runs on the
-                # pre-pass's side stream, behind the pre-pass and behind the tower kernel that produced its gradients,
-                # beside the tower's weight-gradient kernels (which stay on the main stream).  DenseSlab.join() brings
-                # the streams together at the end of the step.
-                side = ctx.seg_event[0]      # (already waiting for the tower + head launch: mlp.TowerHeadFunction)
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                ws, ws_n, pre = plan.update_workspace_for(ids_t, ctx.seg_event, B)
-                wd = ctypes.byref(inline) if (inline is not None and g_wd is not None and g_w is None) else None
-                L.check(lib.dctr_embed_update(cplan, plan.units_ptr(), plan.n_grid_units, plan.max_vocab, _ptr(ids_t),
-                                              _ptr(parts_t), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out, _ptr(fm_s),
-                                              fm_s.stride(0) if fm_s is not None else 0, _ptr(g_fm), _ptr(g_wide),
-                                              plan.ld_wide, opt, lr, eps, _ptr(X), X.stride(0), _ptr(g_wd), wd, _ptr(ws), ws_n, pre,
-                                              L.stream_handle(X.device)), "dctr_embed_update")
-            if side is not None:
-                # (everything the side-stream kernels touch stays allocated until the join)
-                sink.forked(side, (X, out, ids_t, parts_t, fm_s, g_out, g_fm, g_wide, g_wd, ws, den_t, amax))
-            return None, None, None, g_w, None, None
-
-        # general path (pooled VarLen fields, shared tables, very large batches): atomic scatter (+ consume pass)
-        if kind == "sgd" and not plan.has_maxpool:
-            cplan = plan.bind(X.device)
-            L.check(lib.dctr_embed_bwd(cplan, _ptr(X), X.stride(0), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out,
-                                       _ptr(g_fm), _ptr(g_wide), L.BWD_SGD, float(update[1]), stream),
-                    "dctr_embed_bwd(sgd)")
-            return None, None, None, g_w, None, None
-
-        plan.ensure_gacc()
-        if kind == "dense":
-            plan.prepare_dense_grads()
+    # general path (pooled VarLen fields, shared tables, very large batches): atomic scatter (+ consume pass)
+    if kind == "sgd" and not plan.has_maxpool:
         cplan = plan.bind(X.device)
         L.check(lib.dctr_embed_bwd(cplan, _ptr(X), X.stride(0), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out,
-                                   _ptr(g_fm), _ptr(g_wide), L.BWD_ACCUM, 0.0, stream), "dctr_embed_bwd(accum)")
-        if kind in ("sgd", "sgd2"):
-            L.check(lib.dctr_embed_apply(cplan, _ptr(X), X.stride(0), B, L.OPT_SGD, float(update[1]), 0.0, stream),
-                    "dctr_embed_apply(sgd)")
-        elif kind == "adagrad":
-            L.check(lib.dctr_embed_apply(cplan, _ptr(X), X.stride(0), B, L.OPT_ADAGRAD, float(update[1]),
-                                         float(update[2]), stream), "dctr_embed_apply(adagrad)")
-        elif kind != "dense":
-            raise RuntimeError("unknown sparse update mode %r" % (kind,))
-        return None, None, None, g_w, None, None
+                                   _ptr(g_fm), _ptr(g_wide), L.BWD_SGD, float(update[1]), stream),
+                "dctr_embed_bwd(sgd)")
+        return
+
+    plan.ensure_gacc()
+    if kind == "dense":
+        plan.prepare_dense_grads()
+    cplan = plan.bind(X.device)
+    L.check(lib.dctr_embed_bwd(cplan, _ptr(X), X.stride(0), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out,
+                               _ptr(g_fm), _ptr(g_wide), L.BWD_ACCUM, 0.0, stream), "dctr_embed_bwd(accum)")
+    if kind in ("sgd", "sgd2"):
+        L.check(lib.dctr_embed_apply(cplan, _ptr(X), X.stride(0), B, L.OPT_SGD, float(update[1]), 0.0, stream),
+                "dctr_embed_apply(sgd)")
+    elif kind == "adagrad":
+        L.check(lib.dctr_embed_apply(cplan, _ptr(X), X.stride(0), B, L.OPT_ADAGRAD, float(update[1]),
+                                     float(update[2]), stream), "dctr_embed_apply(adagrad)")
+    elif kind != "dense":
+        raise RuntimeError("unknown sparse update mode %r" % (kind,))
 
 
 def embed(plan, X, want_fm=False, full=False):
@@ -275,6 +292,91 @@ def embed(plan, X, want_fm=False, full=False):
     if plan.has_lookup and not full:
         out = out[:, :plan.width]
     return out, wide, fm
+
+
+# ---- ONN's pair lookup (models/onn.py:98-120; csrc/pair_embed.hip) ---------------------------------------------------
+class PairEmbedFunction(torch.autograd.Function):
+    """Lookup through a pair plan (``EmbeddingPlan(pair=True)``): ``out [B, ld_out]`` = the P products ``emb1_p[id_i] *
+    emb2_p[id_j]`` followed by the dense block, ``wide [B]`` the first-order logit -- ``dctr_pair_embed_fwd``.  The backward
+    turns the gradient of ``out`` into row gradients (``dctr_pair_embed_bwd``: ``g_rows [B, ld_rows]``, field f's slice at
+    its ``out_off``) and hands them to the update ``plan.update`` selects, exactly as ``EmbedFunction.backward`` does."""
+
+    @staticmethod
+    def forward(ctx, plan, X, anchor, wdense_w, for_backward=False):
+        lib = L.lib()
+        X = _rows_f32(X, "model input X")
+        if X.shape[1] < plan.n_xcols:
+            raise ValueError("X has %d columns, the feature columns need %d" % (X.shape[1], plan.n_xcols))
+        B = X.shape[0]
+        cplan = plan.bind(X.device)
+        out = torch.empty((B, plan.ld_out), dtype=torch.float32, device=X.device) if plan.has_lookup else None
+        wide = torch.empty((B,), dtype=torch.float32, device=X.device) if plan.has_wide else None
+        lazy = plan.lazy if plan.update[0] == "lazy" else None
+        if lazy is not None:
+            if for_backward and lazy.plan is plan:
+                lazy.catchup(X)
+            else:
+                lazy.flush()
+        ids_t = parts_t = den_t = amax = None
+        ctx.seg_event = None
+        stream = L.stream_handle(X.device)
+        if for_backward and plan.table_params and plan.update_kernel_ok(B):
+            ids_t = torch.empty((plan.n_vcols, B), dtype=torch.int32, device=X.device)
+            parts_t = torch.empty((plan.n_vcols, B), dtype=torch.int16, device=X.device)
+            den_t, amax = plan.step_buffers(B, X.device)
+        plan.point_step_buffers(den_t, amax)
+        if ids_t is not None:
+            L.check(lib.dctr_embed_ids(cplan, plan.units_ptr(), plan.n_grid_units, _ptr(X), X.stride(0), B, _ptr(ids_t),
+                                       _ptr(parts_t), stream), "dctr_embed_ids")
+            if plan.segments_enabled():
+                ctx.seg_event = plan.launch_segments(ids_t, parts_t, B)
+        err = plan.err_flag(X.device)
+        L.check(lib.dctr_pair_embed_fwd(cplan, _ptr(X), X.stride(0), B, _ptr(out), plan.ld_out, _ptr(wide), 1, _ptr(err),
+                                        stream), "dctr_pair_embed_fwd")
+        ctx.plan = plan
+        ctx.save_for_backward(X, ids_t, parts_t, den_t, amax)
+        ctx.set_materialize_grads(False)
+        return (out if out is not None else X.new_zeros((B, 0)), wide if wide is not None else X.new_zeros((B,)))
+
+    @staticmethod
+    def backward(ctx, g_out, g_wide):
+        lib = L.lib()
+        plan = ctx.plan
+        X, ids_t, parts_t, den_t, amax = ctx.saved_tensors
+        B = X.shape[0]
+        plan.point_step_buffers(den_t, amax)
+        if not plan.deep:
+            g_out = None
+        if not plan.has_wide:
+            g_wide = None
+        g_wide, g_wd, g_w = _wide_dense_grad(plan, X, g_wide, ids_t, ctx.needs_input_grad[3])
+        if (g_out is None and g_wide is None) or not plan.table_params:
+            return None, None, None, g_w, None
+        g_rows, ld_rows = None, 0
+        if g_out is not None:
+            g_out, ld_g = _aligned_rows(g_out, plan.vec, 0)
+            ld_rows = plan.ld_rows
+            g_rows = torch.empty((B, ld_rows), dtype=torch.float32, device=X.device)
+            L.check(lib.dctr_pair_embed_bwd(plan.bind(X.device), _ptr(X), X.stride(0), B, _ptr(g_out), ld_g, _ptr(g_rows),
+                                            ld_rows, L.stream_handle(X.device)), "dctr_pair_embed_bwd")
+        _update_tables(plan, X, ids_t, parts_t, ctx.seg_event, g_rows, ld_rows, None, None, None, g_wide, g_wd, g_w, den_t,
+                       amax)
+        return None, None, None, g_w, None
+
+
+def pair_embed(plan, X, full=False):
+    """(out [B, width] view, wide [B]) of ONN's pair lookup for model input ``X`` under the pair plan ``plan``; ``full``
+    returns the un-sliced ``[B, ld_out]`` buffer (what the MFMA tower reads in place)."""
+    L.require_gpu(X, "model input X")
+    if not getattr(plan, "pair", False):
+        raise ValueError("pair_embed needs a pair plan (EmbeddingPlan(pair=True))")
+    if getattr(plan, "sharder", None) is not None or getattr(plan, "exchange", None) is not None:
+        raise NotImplementedError("the pair lookup (ONN) is not wired into the multi-GPU trainers")
+    plan.bind(X.device)
+    out, wide = PairEmbedFunction.apply(plan, X, plan.anchor, plan.wide_dense_weight, torch.is_grad_enabled())
+    if plan.has_lookup and not full:
+        out = out[:, :plan.width]
+    return out, wide
 
 
 _PLAN_CACHE_ATTR = "_dctr_plans"

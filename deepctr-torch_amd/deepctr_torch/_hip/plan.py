@@ -363,21 +363,46 @@ class EmbeddingPlan(object):
     ``wide_per_field``: the gather hands the first-order weights out PER FIELD instead of summed (``wide [B, ld_wide]``:
     column f = wide field f, column ``n_wide`` = the dense half of Linear) and the update reads their gradient in the
     same layout (DCTR_PLAN_WIDE_PER_FIELD, include/dctr.h) -- IFM / DIFM re-weight them per sample before the sum.
+
+    ``deep_fields``: the deep side as an explicit list of ``(name, table parameter, X column)`` -- fixed-length fields,
+    each over the table given -- instead of feature columns over ``deep_tables`` (``deep_columns`` then only supplies the
+    dense block).  ``pair`` (needs ``deep_fields``, an even number of one common dim D): fields 2p / 2p+1 are emb1 / emb2
+    of ONN's pair p (csrc/pair_embed.hip).  The lookup's output row is then ``[P products of D | dense]``
+    (``width = P * D + n_dense``, ``ld_out`` follows it) while a field's ``out_off`` is its offset in a ROW-GRADIENT row of
+    ``2 P D`` floats (stride ``ld_rows``): what the pair backward writes and the update kernels read as their ``g_out``.
     """
 
     def __init__(self, feature_index, deep_columns=(), deep_tables=None, wide_columns=(), wide_tables=None,
-                 wide_dense_weight=None, unpooled=False, with_dense=True, wide_per_field=False):
+                 wide_dense_weight=None, unpooled=False, with_dense=True, wide_per_field=False, deep_fields=None,
+                 pair=False):
         self.feature_index = feature_index
         self.wide_per_field = bool(wide_per_field)
+        self.pair = bool(pair)
         self.n_xcols = max([hi for (_, hi) in feature_index.values()] + [1])
-        dfix, dpool, emb_width = _fields_for(deep_columns, deep_tables, feature_index, unpooled) \
-            if deep_tables is not None else ([], [], 0)
+        if deep_fields is not None:
+            if deep_tables is not None:
+                raise ValueError("deep_fields and deep_tables are two ways to name the deep side: give one")
+            dfix, dpool, emb_width = [], [], 0
+            for name, param, col in deep_fields:
+                dfix.append(_FieldSpec(name, param, int(col), 1, 0, -1, emb_width))
+                emb_width += int(param.shape[1])
+        else:
+            dfix, dpool, emb_width = _fields_for(deep_columns, deep_tables, feature_index, unpooled) \
+                if deep_tables is not None else ([], [], 0)
+        if self.pair:
+            if deep_fields is None or len(dfix) % 2 or len(set(f.dim for f in dfix)) > 1 or self.wide_per_field:
+                raise ValueError("a pair plan takes an even number of explicit deep fields of one common dim "
+                                 "(and no per-field wide side)")
         wfix, wpool, _ = _fields_for(wide_columns, wide_tables, feature_index, False) \
             if wide_tables is not None else ([], [], 0)
         self.deep = dfix + dpool
         self.wide = wfix + wpool
         self.n_deep_fixed, self.n_wide_fixed = len(dfix), len(wfix)
         self.ld_wide = len(self.wide) + 1 if self.wide_per_field else 1      # floats per sample of `wide` / `g_wide`
+        # pair mode: the output row holds one product per PAIR; the fields' out_off address the row-gradient row
+        self.ld_rows = max(4, (emb_width + 3) // 4 * 4) if self.pair else 0
+        if self.pair:
+            emb_width //= 2
         self.emb_width = emb_width
         dims = sorted(set(f.dim for f in self.deep))
         self.emb_dim = dims[0] if len(dims) == 1 else 0
@@ -579,6 +604,8 @@ class EmbeddingPlan(object):
         self.__dict__.update(d)
         self.__dict__.setdefault("wide_per_field", False)      # (a plan pickled before the mode existed)
         self.__dict__.setdefault("ld_wide", 1)
+        self.__dict__.setdefault("pair", False)
+        self.__dict__.setdefault("ld_rows", 0)
         self._reset_device_image()
 
     # ---- sparse-update mode (see ops.py) ---------------------------------------------------------

@@ -10,9 +10,10 @@ from .difm import DIFM
 from .fibinet import FiBiNET
 from .ifm import IFM
 from .nfm import NFM
+from .onn import ONN
 from .pnn import PNN
 from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM"]
+           "IFM", "DIFM", "ONN"]

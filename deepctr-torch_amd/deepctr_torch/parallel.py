@@ -119,6 +119,11 @@ def _refuse_wide_per_field(plan, who):
     if getattr(plan, "wide_per_field", False):
         raise NotImplementedError("%s: this model's plan hands out per-field first-order weights (IFM / DIFM); "
                                   "multi-GPU training of these models is not implemented -- train on one GPU" % who)
+    # ONN's pair lookup (EmbeddingPlan(pair=True)): its row gradients come out of a backward kernel of its own, which
+    # neither the all-gathered payload nor the table-sharded exchange carries
+    if getattr(plan, "pair", False):
+        raise NotImplementedError("%s: this model looks its tables up through the pair lookup (ONN); multi-GPU "
+                                  "training of this model is not implemented -- train on one GPU" % who)
 
 
 class DataParallelTrainer(object):

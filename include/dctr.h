@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 27
+#define DCTR_ABI_VERSION 28
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -348,6 +348,34 @@ int dctr_bi_pooling_fwd(const float* G, int64_t ld_g, int32_t B, int32_t F, int3
 int dctr_bi_pooling_bwd(const float* G, int64_t ld_g, int32_t B, int32_t F, int32_t D, int32_t dense_off,
                         int32_t n_dense, const float* gout, int64_t ld_go, float* gG, int64_t ld_gg,
                         dctr_stream_t stream);
+
+/* ---- ONN / NFFM: the second-order pair lookup (models/onn.py:14-34, :98-120, :139-148; csrc/pair_embed.hip) ---------
+ * Every ordered pair p = (i < j) of sparse features owns two tables: emb1 indexed by feature i's id, emb2 by feature j's
+ * (pairs in the reference's order: i ascending, then j).  The reference runs 2 P aten::embedding calls, P multiplies and a
+ * cat, and 2 P dense [V, D] gradients backward; here one launch per direction.
+ *   plan->deep holds 2 P FIXED-LENGTH fields of one common dim D: fields 2p and 2p + 1 are emb1 and emb2 of pair p, each
+ *   with its own X column, table pointer, ld (row stride; 0 = D), vocab, and an out_off that is its offset in a
+ *   ROW-GRADIENT row (2 p D and (2 p + 1) D) -- not in `out`, which holds one slice per PAIR.
+ * forward:
+ *   out[b, p D + d] = T_{2p}[id(b, col_{2p})][d] * T_{2p+1}[id(b, col_{2p+1})][d]      (one fp32 multiply)
+ *   out[b, P D + k] = X[b, dense_cols[k]]   when plan->dense_off >= 0 (it must equal P D): combined_dnn_input's order
+ *   (inputs.py:126-138); ld_out >= P D + n_dense, a multiple of plan->vec (gather buffers are padded to 4)
+ *   wide[b * ld_wide] = the first-order logit exactly as dctr_embed_fwd computes it for the same plan -- the same device
+ *   code (csrc/embed_tile.hpp), the same bits (nullable; a max-pooled wide field's arg-max goes to ext->amax likewise)
+ *   err: bit 0 is set when an id falls outside [0, vocab); such a row reads as row 0 (nullable)
+ * backward (re-reads the rows; nothing of size [B, 2 P D] is saved by the forward):
+ *   g_rows[b, out_off_{2p}   + d] = g_out[b, p D + d] * T_{2p+1}[id(b, col_{2p+1})][d]
+ *   g_rows[b, out_off_{2p+1} + d] = g_out[b, p D + d] * T_{2p}[id(b, col_{2p})][d]
+ *   g_rows [B, ld_rows] is then what dctr_embed_update / dctr_embed_update_lazy / dctr_embed_bwd take as their g_out
+ *   (ld_g = ld_rows): fixed-length fields over distinct tables are simple units.  Columns outside the 2 P slices are not
+ *   written.  No atomics, no scratch.
+ * plan->vec (4 / 2 / 1) is honoured -- D need not be a multiple of 4.  Refused with DCTR_ENOSUP: pooled or VarLen deep
+ * fields (n_deep_fixed != n_deep), deep fields of different dims, plan->out_chunks, DCTR_PLAN_WIDE_PER_FIELD, an odd
+ * n_deep, more than 65535 pairs, a tile beyond the LDS.                                                              */
+int dctr_pair_embed_fwd(const dctr_plan_t* plan, const float* X, int64_t ldx, int32_t B, float* out, int64_t ld_out,
+                        float* wide, int64_t ld_wide, int32_t* err, dctr_stream_t stream);
+int dctr_pair_embed_bwd(const dctr_plan_t* plan, const float* X, int64_t ldx, int32_t B, const float* g_out, int64_t ld_g,
+                        float* g_rows, int64_t ld_rows, dctr_stream_t stream);
 
 /* ---- AFMLayer (interaction.py:251-325): attentional pooling of the pairwise products (csrc/afm.hip) -----------
  *   bi_k = e_i (.) e_j (pairs i < j, itertools.combinations order);  t_k = relu(bi_k W + bias);  s_k = t_k . h;
