@@ -576,6 +576,53 @@ class AFMFunction(torch.autograd.Function):
         return gE, gW, gb, gh.reshape(ctx.shapes[0]), gp.reshape(ctx.shapes[1])
 
 
+class CCPMConvFunction(torch.autograd.Function):
+    """ConvLayer of CCPM on ``E [B, F, D]`` (csrc/ccpm.hip): ``(E, params, widths, filters, ks, keep) -> [B, C_L * k_L * D]``.
+    ``params`` is the packed vector the kernel reads (weight, bias of layer 1, then layer 2, ...).  With ``keep`` (a
+    backward will follow) the forward also records the field every pooled element came from, one byte each, and the
+    backward routes by it; without (``predict``) the kernel gets no selection buffer."""
+
+    @staticmethod
+    def forward(ctx, E, params, widths, filters, ks, keep):
+        lib = L.lib()
+        E, lde = _rows3(E, "CCPM conv input")
+        B, F, D = E.shape
+        P = params.detach().float().contiguous()
+        nl = len(filters)
+        arrs = tuple((ctypes.c_int32 * nl)(*[int(v) for v in a]) for a in (widths, filters, ks))
+        n_out = int(filters[-1]) * int(ks[-1]) * D
+        n_sel = sum(int(c) * int(k) for c, k in zip(filters, ks)) * D
+        sel = torch.empty((B, n_sel), dtype=torch.uint8, device=E.device) if keep else None
+        out = torch.empty((B, n_out), dtype=torch.float32, device=E.device)
+        L.check(lib.dctr_ccpm_fwd(_ptr(E), lde, B, F, D, nl, arrs[0], arrs[1], arrs[2], _ptr(P), _ptr(out), n_out,
+                                  _ptr(sel), L.stream_handle(E.device)), "dctr_ccpm_fwd")
+        if keep:
+            ctx.save_for_backward(E, P, sel)
+            ctx.spec = (tuple(widths), tuple(filters), tuple(ks))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = L.lib()
+        E, P, sel = ctx.saved_tensors
+        widths, filters, ks = ctx.spec
+        E, lde = _rows3(E, "CCPM conv input")
+        B, F, D = E.shape
+        dev = E.device
+        nl = len(filters)
+        arrs = tuple((ctypes.c_int32 * nl)(*[int(v) for v in a]) for a in (widths, filters, ks))
+        if gout.dtype != torch.float32 or gout.dim() != 2 or (gout.shape[1] > 1 and gout.stride(1) != 1) or \
+                (B > 1 and gout.stride(0) < gout.shape[1]):
+            gout = gout.float().contiguous()
+        gE = torch.empty((B, F, D), dtype=torch.float32, device=dev)
+        gP = torch.empty_like(P)
+        ws = torch.empty((max(1, lib.dctr_ccpm_bwd_workspace_floats(B, P.numel())),), dtype=torch.float32, device=dev)
+        L.check(lib.dctr_ccpm_bwd(_ptr(E), lde, B, F, D, nl, arrs[0], arrs[1], arrs[2], _ptr(P), _ptr(sel), _ptr(gout),
+                                  gout.stride(0) if B > 1 else gout.shape[1], _ptr(gE), F * D, _ptr(gP), _ptr(ws),
+                                  L.stream_handle(dev)), "dctr_ccpm_bwd")
+        return gE, gP, None, None, None, None
+
+
 class BiPoolFunction(torch.autograd.Function):
     """BiInteractionPooling on the gather's rows (csrc/fm.hip): ``G [B, ld]`` (fields first, dense block at
     ``dense_off``) -> ``[B, r4(D + n_dense)]`` = ``[bi | dense]``, the NFM tower's input; the backward hands back a

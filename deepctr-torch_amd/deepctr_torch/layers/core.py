@@ -2,6 +2,7 @@
 Same parameters / ``state_dict`` keys as the reference (layers/core.py:67-160)."""
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .activation import activation_layer
 
@@ -52,3 +53,31 @@ class PredictionLayer(nn.Module):
     def forward(self, X):
         out = X + self.bias if self.use_bias else X
         return torch.sigmoid(out) if self.task == "binary" else out
+
+
+def same_padding(size, kernel, stride=1, dilation=1):
+    """``(before, after)`` zeros along one axis under TensorFlow's 'SAME' rule: as many as a window of ``kernel`` taps
+    needs to produce ``ceil(size / stride)`` outputs, split evenly, the odd one going AFTER the data."""
+    outputs = -(-size // stride)
+    total = max((outputs - 1) * stride + (kernel - 1) * dilation + 1 - size, 0)
+    return total // 2, total - total // 2
+
+
+class Conv2dSame(nn.Conv2d):
+    """``nn.Conv2d`` under 'SAME' padding (the layer of reference layers/core.py:163-185; same constructor -- its
+    ``padding`` argument is accepted and unused, as there): the zeros of ``same_padding`` are put around the input, then
+    the unpadded convolution runs.  Construction draws ``nn.Conv2d``'s own initialisation and then ``xavier_uniform_`` on
+    the weight, the order in which the reference consumes the generator.  ``ConvLayer`` runs its whole stack as one kernel
+    and calls this ``forward`` only for inputs outside it."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride=stride, padding=0, dilation=dilation,
+                           groups=groups, bias=bias)
+        nn.init.xavier_uniform_(self.weight)
+
+    def forward(self, x):
+        rows, cols = (same_padding(x.shape[ax - 2], self.kernel_size[ax], self.stride[ax], self.dilation[ax])
+                      for ax in (0, 1))
+        if any(rows + cols):
+            x = F.pad(x, cols + rows)                     # (F.pad lists the last axis first)
+        return self._conv_forward(x, self.weight, self.bias)

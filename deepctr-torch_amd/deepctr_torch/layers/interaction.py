@@ -9,8 +9,10 @@ import torch.nn as nn
 from .._hip import lib as _lib
 from .._hip import ops as _ops
 from .activation import Identity, activation_layer
+from .core import Conv2dSame
+from .sequence import KMaxPooling
 
-__all__ = ["FM", "BiInteractionPooling", "AFMLayer", "InteractingLayer", "CrossNetMix", "CIN", "SENETLayer", "BilinearInteraction", "InnerProductLayer", "OutterProductLayer", "CrossNet"]
+__all__ = ["FM", "BiInteractionPooling", "AFMLayer", "InteractingLayer", "CrossNetMix", "CIN", "SENETLayer", "BilinearInteraction", "InnerProductLayer", "OutterProductLayer", "CrossNet", "ConvLayer", "ccpm_pool_sizes"]
 
 
 class FM(nn.Module):
@@ -511,3 +513,79 @@ class CrossNet(nn.Module):
         for i in range(self.layer_num):   # x0 * (W x_l + b) + x_l
             x_l = x_0 * (torch.addmm(self.bias[i].t(), x_l, self.kernels[i].t())) + x_l
         return x_l
+
+
+def ccpm_pool_sizes(field_size, n_layers):
+    """Rows every layer of CCPM's conv stack keeps (the flexible p-max pooling of the paper, as reference
+    interaction.py:704-711 evaluates it): layer i of L asks for ``int((1 - (i / L) ** (L - i)) * n)`` rows, at least 1, the
+    last layer for 3 -- and a layer never keeps more rows than it is given."""
+    n = int(field_size)
+    sizes, rows = [], n
+    for i in range(1, n_layers + 1):
+        wanted = 3 if i == n_layers else max(1, int((1 - pow(i / n_layers, n_layers - i)) * n))
+        rows = min(wanted, rows)
+        sizes.append(rows)
+    return sizes
+
+
+class ConvLayer(nn.Module):
+    """Conv layer of CCPM: per layer a (width, 1) 'SAME' convolution over the field axis, ``tanh`` and k-max pooling over
+    the fields -- ``[B, 1, field_size, D] -> [B, conv_filters[-1], filed_shape, D]`` (reference interaction.py:675-717;
+    same constructor, an ``nn.Sequential`` of ``Conv2dSame / Tanh / KMaxPooling`` per layer and therefore the same
+    ``conv_layer.{0,3,6,...}.{weight,bias}`` keys, the pooling sizes of ``ccpm_pool_sizes``, ``filed_shape`` with its
+    spelling).
+
+    One kernel forward, one backward (``csrc/ccpm.hip``): a wave owns a sample, every layer's image stays in LDS, the
+    forward records which field each pooled element came from (one byte) and the backward routes by it.  Equal values of
+    a column keep their field order.  Inputs outside the kernel (``_kernel_fits``; anything but float32) run the
+    ``Sequential`` as PyTorch-ROCm ops."""
+
+    def __init__(self, field_size, conv_kernel_width, conv_filters, device='cpu'):
+        super(ConvLayer, self).__init__()
+        self.device = device
+        filters = [int(c) for c in conv_filters]
+        ks = ccpm_pool_sizes(field_size, len(filters))
+        stages = []
+        for n, (cin, cout, k) in enumerate(zip([1] + filters[:-1], filters, ks)):
+            stages += [Conv2dSame(cin, cout, (conv_kernel_width[n], 1), stride=1), nn.Tanh(), KMaxPooling(k, 2, device)]
+        self.conv_layer = nn.Sequential(*stages)
+        self.filed_shape = ks[-1] if ks else int(field_size)
+        self.to(device)
+
+    def _spec(self):
+        """(widths, filters, ks) of the stack, read from the modules."""
+        convs = [m for m in self.conv_layer if isinstance(m, Conv2dSame)]
+        pools = [m for m in self.conv_layer if isinstance(m, KMaxPooling)]
+        return ([int(c.weight.shape[2]) for c in convs], [int(c.weight.shape[0]) for c in convs],
+                [int(p.k) for p in pools])
+
+    @staticmethod
+    def _kernel_fits(F, D, widths, filters, ks):
+        """csrc/ccpm.hip: F <= 64, D <= 64, at most 4 layers, filters <= 16, widths <= 16, 1 <= k_i <= rows of its input,
+        and the forward's and the backward's per-sample LDS images (include/dctr.h spells them out) within 64 KB each."""
+        L = len(filters)
+        if L < 1 or L > 4 or len(widths) != L or len(ks) != L or F < 1 or D < 1 or F > 64 or D > 64:
+            return False
+        C, n = [1] + list(filters), [F] + list(ks)
+        if any(c < 1 or c > 16 for c in filters) or any(w < 1 or w > 16 for w in widths):
+            return False
+        if any(n[i] < 1 or n[i] > n[i - 1] for i in range(1, L + 1)):
+            return False
+        n_params = sum(C[i] * C[i - 1] * widths[i - 1] + C[i] for i in range(1, L + 1))
+        img = [C[i] * n[i] * D for i in range(L + 1)]
+        max_act = max(C[i] * n[i - 1] * D for i in range(1, L + 1))
+        fwd = 4 * (n_params + max(img) + max_act)
+        bwd = 4 * (2 * n_params + sum(img) + 2 * max(img)) + (sum(img[1:]) + 3) // 4 * 4
+        return fwd <= 64 * 1024 and bwd <= 64 * 1024
+
+    def forward(self, inputs):
+        widths, filters, ks = self._spec()
+        convs = [m for m in self.conv_layer if isinstance(m, Conv2dSame)]
+        if inputs.dim() != 4 or inputs.shape[1] != 1 or inputs.dtype != torch.float32 or \
+                any(c.bias is None or c.weight.dtype != torch.float32 for c in convs) or \
+                not self._kernel_fits(inputs.shape[2], inputs.shape[3], widths, filters, ks):
+            return self.conv_layer(inputs)
+        params = torch.cat([t.reshape(-1) for c in convs for t in (c.weight, c.bias)])
+        keep = torch.is_grad_enabled() and (inputs.requires_grad or params.requires_grad)
+        out = _ops.CCPMConvFunction.apply(inputs.squeeze(1), params, tuple(widths), tuple(filters), tuple(ks), keep)
+        return out.view(inputs.shape[0], filters[-1], ks[-1], inputs.shape[3])

@@ -46,3 +46,24 @@ class SequencePoolingLayer(nn.Module):
         if self.mode == 'mean':
             total = total / (count + self.eps.to(count.device)).unsqueeze(-1)
         return total
+
+
+class KMaxPooling(nn.Module):
+    """The ``k`` largest values along ``axis``, largest first (the layer of reference layers/sequence.py:157-189; same
+    constructor, same two ``ValueError`` texts).  ``ConvLayer`` fuses it with the convolution in front of it
+    (``csrc/ccpm.hip``, where equal values keep their order along the axis) and calls this ``forward`` only for inputs
+    outside that kernel."""
+
+    def __init__(self, k, axis, device='cpu'):
+        super(KMaxPooling, self).__init__()
+        self.k, self.axis = k, axis
+        self.to(device)
+
+    def forward(self, inputs):
+        rank = inputs.dim()
+        if not 0 <= self.axis < rank:
+            raise ValueError("axis must be 0~%d,now is %d" % (rank - 1, self.axis))
+        size = inputs.shape[self.axis]
+        if not 1 <= self.k <= size:
+            raise ValueError("k must be in 1 ~ %d,now k is %d" % (size, self.k))
+        return inputs.topk(self.k, dim=self.axis, largest=True, sorted=True).values

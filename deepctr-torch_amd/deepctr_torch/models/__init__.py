@@ -3,6 +3,7 @@ and ``state_dict`` keys are the reference's (``deepctr_torch/models/*.py``)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .basemodel import BaseModel, Linear
+from .ccpm import CCPM
 from .dcn import DCN
 from .dcnmix import DCNMix
 from .deepfm import DeepFM
@@ -16,4 +17,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN"]
+           "IFM", "DIFM", "ONN", "CCPM"]

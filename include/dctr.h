@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 28
+#define DCTR_ABI_VERSION 29
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -390,6 +390,33 @@ int dctr_afm_fwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, 
 int dctr_afm_bwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, int32_t A, const float* W,
                  const float* bias, const float* h, const float* p, const float* gy, float* gE, int64_t ld_ge,
                  float* gW, float* gbias, float* gh, float* gp, float* workspace, dctr_stream_t stream);
+
+/* ---- ConvLayer of CCPM (interaction.py:675-717: Conv2dSame / Tanh / KMaxPooling per layer; csrc/ccpm.hip) -------
+ * Layers i = 1..n_layers on one sample's image x [C_{i-1}][n_{i-1}][D];  C_0 = 1, C_i = filters[i-1];  n_0 = F, n_i = k[i-1]:
+ *   a[co, f, d] = bias[co] + sum_ci sum_t W[co, ci, t] * x[ci, f + t - top, d]      w = width[i-1], top = (w - 1) / 2
+ *                 (cross-correlation; rows outside [0, n_{i-1}) are 0: top zero rows above, w - 1 - top below)
+ *   y = tanh(a);  per column (co, d) the k_i largest y over f, in descending order (torch.topk(sorted=True)).
+ *   TIE RULE: equal values keep their field order, the lower index first (the reference leaves ties unspecified).
+ * E [B, F, D] rows at E + b*ld_e;  out [B, C_L * k_L * D] ([C_L][k_L][D] per sample) rows at out + b*ld_out.
+ * width / filters / k are HOST arrays of n_layers entries, 1 <= k[i-1] <= n_{i-1}.  params is one device vector: layer 1
+ * weight [C_1, C_0, w_1] (the nn.Conv2d weight), layer 1 bias [C_1], layer 2 weight, ...; g_params has the same layout.
+ * sel: one byte per pooled element of every layer, [B][sum_i C_i * k_i * D] (per sample: layer 1 [C_1][k_1][D], layer 2,
+ * ...), the row f each pooled element came from; the forward writes it when the pointer is not NULL.  The backward routes
+ * the gradient by sel and recomputes the selected activations from E; nothing else is saved.  It writes gE [B, F*D] rows
+ * at gE + b*ld_ge and g_params (fixed-order sums, no atomics: identical bits from run to run); workspace:
+ * dctr_ccpm_bwd_workspace_floats(B, n_params) floats, n_params = sum_i (C_i * C_{i-1} * w_i + C_i).
+ * One wave per sample, everything between E and out stays in LDS.  B == 0 returns DCTR_OK before any buffer check.
+ * DCTR_ENOSUP unless F <= 64, D <= 64, n_layers <= 4, C_i <= 16, w_i <= 16 and both per-sample LDS images fit 64 KB (two or
+ * more workgroups per CU), with img_i = C_i * n_i * D, max_img = max_{i>=0} img_i, max_act = max_{i>=1} C_i * n_{i-1} * D:
+ *   forward   4 * (n_params + max_img + max_act)
+ *   backward  4 * (2 * n_params + sum_{i>=0} img_i + 2 * max_img) + sum_{i>=1} img_i                                    */
+size_t dctr_ccpm_bwd_workspace_floats(int32_t B, int32_t n_params);
+int dctr_ccpm_fwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, int32_t n_layers, const int32_t* width,
+                  const int32_t* filters, const int32_t* k, const float* params, float* out, int64_t ld_out, uint8_t* sel,
+                  dctr_stream_t stream);
+int dctr_ccpm_bwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, int32_t n_layers, const int32_t* width,
+                  const int32_t* filters, const int32_t* k, const float* params, const uint8_t* sel, const float* g_out,
+                  int64_t ld_gout, float* gE, int64_t ld_ge, float* g_params, float* workspace, dctr_stream_t stream);
 
 /* ---- InteractingLayer of AutoInt (interaction.py:328-394): multi-head self-attention over the fields (csrc/interact.hip)
  *   Q = E Wq, K = E Wk, V = E Wv;  head n = columns [n*A, (n+1)*A), A = D / H;  P_n = softmax_rows(Q_n K_n^T (/ sqrt(A)
