@@ -623,6 +623,87 @@ class CCPMConvFunction(torch.autograd.Function):
         return gE, gP, None, None, None, None
 
 
+DIN_ACT = {"linear": 0, "relu": 1, "sigmoid": 2, "prelu": 3, "dice": 4}     # include/dctr.h, dctr_din_attn_fwd
+
+
+def _i32s(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
+def _i64s(values):
+    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
+
+
+def din_attention_supported(T, dims, hidden, act):
+    """True when csrc/din.hip runs this shape: E = sum(dims) <= 64, at most 4 segments, 1 <= T <= 128, 1 to 3 hidden
+    layers of at most 128 units, ``act`` one of ``DIN_ACT``."""
+    if act not in DIN_ACT or not dims or not hidden:
+        return False
+    return bool(L.lib().dctr_din_attn_supported(int(T), len(dims), _i32s(dims), len(hidden), _i32s(hidden), DIN_ACT[act]))
+
+
+def _rows2(t, what):
+    """[B, W] float32 with unit stride inside a row (views of the gather's output pass through without a copy)"""
+    L.require_gpu(t, what)
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or \
+            (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.float().contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+class DINAttentionFunction(torch.autograd.Function):
+    """AttentionSequencePoolingLayer (csrc/din.hip): ``(Q [B, ld_q], K [B, ld_k] | None, params, segs, T, hidden, act,
+    softmax, lengths [B] int32 | None, mask [B, T] uint8 | None, keep) -> [B, E]``.
+
+    ``segs``: one ``(dim, q_off, k_off, k_step)`` per history feature: where its query and its first key start inside a
+    row of Q / K and how far apart two positions lie.  ``K = None``: the keys lie in Q's rows (the model's gathered row) and
+    ONE gradient row comes back.  ``params``: the packed vector the kernel reads (include/dctr.h).  ``keep``: a backward
+    will follow, so the forward also writes the ``[B, T]`` weights; everything else is recomputed."""
+
+    @staticmethod
+    def forward(ctx, Q, K, params, segs, T, hidden, act, softmax, lengths, mask, keep):
+        lib = L.lib()
+        Q, ldq = _rows2(Q, "DIN attention query")
+        shared = K is None
+        Kt, ldk = (Q, ldq) if shared else _rows2(K, "DIN attention keys")
+        B = Q.shape[0]
+        P = params.detach().float().contiguous()
+        dims, qo, ko, ks = zip(*segs)
+        E = int(sum(dims))
+        out = torch.empty((B, E), dtype=torch.float32, device=Q.device)
+        wts = torch.empty((B, int(T)), dtype=torch.float32, device=Q.device) if keep else None
+        cargs = (int(T), len(dims), _i32s(dims), _i64s(qo), _i64s(ko), _i64s(ks), _ptr(lengths), _ptr(mask), len(hidden),
+                 _i32s(hidden), DIN_ACT[act], int(bool(softmax)), _ptr(P))
+        L.check(lib.dctr_din_attn_fwd(_ptr(Q), ldq, _ptr(Kt), ldk, B, *(cargs + (_ptr(out), E, _ptr(wts),
+                                                                            L.stream_handle(Q.device)))),
+                "dctr_din_attn_fwd")
+        if keep:
+            ctx.save_for_backward(Q, Kt, P, wts, lengths, mask)
+            ctx.cfg = (shared, tuple(segs), int(T), tuple(hidden), act, bool(softmax))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = L.lib()
+        Q, Kt, P, wts, lengths, mask = ctx.saved_tensors
+        shared, segs, T, hidden, act, softmax = ctx.cfg
+        B, dev = Q.shape[0], Q.device
+        ldq = Q.stride(0) if B > 1 else Q.shape[1]
+        ldk = Kt.stride(0) if B > 1 else Kt.shape[1]
+        dims, qo, ko, ks = zip(*segs)
+        gout, ldg = _rows2(gout, "DIN attention gradient")
+        # (zeros: the kernel writes the segments, whatever else the rows hold gets no gradient from here)
+        gQ = torch.zeros(Q.shape, dtype=torch.float32, device=dev)
+        gK = gQ if shared else torch.zeros(Kt.shape, dtype=torch.float32, device=dev)
+        gP = torch.empty_like(P)
+        ws = torch.empty((max(1, lib.dctr_din_attn_bwd_workspace_floats(B, P.numel())),), dtype=torch.float32, device=dev)
+        L.check(lib.dctr_din_attn_bwd(_ptr(Q), ldq, _ptr(Kt), ldk, B, T, len(dims), _i32s(dims), _i64s(qo), _i64s(ko),
+                                      _i64s(ks), _ptr(lengths), _ptr(mask), len(hidden), _i32s(hidden), DIN_ACT[act],
+                                      int(softmax), _ptr(P), _ptr(wts), _ptr(gout), ldg, _ptr(gQ), gQ.shape[1], _ptr(gK),
+                                      gK.shape[1], _ptr(gP), _ptr(ws), L.stream_handle(dev)), "dctr_din_attn_bwd")
+        return gQ, (None if shared else gK), gP, None, None, None, None, None, None, None, None
+
+
 class BiPoolFunction(torch.autograd.Function):
     """BiInteractionPooling on the gather's rows (csrc/fm.hip): ``G [B, ld]`` (fields first, dense block at
     ``dense_off``) -> ``[B, r4(D + n_dense)]`` = ``[bi | dense]``, the NFM tower's input; the backward hands back a

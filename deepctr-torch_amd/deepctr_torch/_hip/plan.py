@@ -64,10 +64,21 @@ class _FieldSpec(object):
         self.vocab, self.dim = int(param.shape[0]), int(param.shape[1])
 
 
+def _unpooled_test(unpooled):
+    """``fc -> bool``: is this VarLen column handed out un-pooled (``unpooled``: True / False, or a collection of names)"""
+    if isinstance(unpooled, bool):
+        return lambda fc: unpooled
+    names = frozenset(unpooled)
+    return lambda fc: fc.name in names
+
+
 def _fields_for(columns, tables, feature_index, unpooled):
     """Fixed-length fields first, then VarLen ones (the order of
-    ``sparse_embedding_list + varlen_sparse_embedding_list``, basemodel.py:380)."""
+    ``sparse_embedding_list + varlen_sparse_embedding_list``, basemodel.py:380).  ``unpooled``: True / False for every
+    VarLen column, or the names of those that stay ``[B, maxlen, D]``: their positions follow the fixed-length fields as
+    fixed fields of their own (column after column, position after position), the pooled columns come last."""
     sparse_cols, varlen_cols, _ = split_columns(columns)
+    keep = _unpooled_test(unpooled)
     fixed, pooled = [], []
     off = 0
     for fc in sparse_cols:
@@ -75,18 +86,23 @@ def _fields_for(columns, tables, feature_index, unpooled):
         fixed.append(_FieldSpec(fc.name, w, feature_index[fc.name][0], 1, 0, -1, off))
         off += int(w.shape[1])
     for fc in varlen_cols:
+        if not keep(fc):
+            continue
         w = tables[fc.embedding_name].weight
         lo, hi = feature_index[fc.name]
-        if unpooled:  # [B, maxlen, D]: every position is its own fixed field
-            for t in range(hi - lo):
-                fixed.append(_FieldSpec("%s[%d]" % (fc.name, t), w, lo + t, 1, 0, -1, off))
-                off += int(w.shape[1])
-        else:
-            if fc.combiner not in ("sum", "mean", "max"):
-                raise ValueError('parameter mode should in [sum, mean, max]')
-            len_col = -1 if fc.length_name is None else feature_index[fc.length_name][0]
-            pooled.append(_FieldSpec(fc.name, w, lo, hi - lo, L.POOL_CODE[fc.combiner], len_col, off))
+        for t in range(hi - lo):  # [B, maxlen, D]: every position is its own fixed field
+            fixed.append(_FieldSpec("%s[%d]" % (fc.name, t), w, lo + t, 1, 0, -1, off))
             off += int(w.shape[1])
+    for fc in varlen_cols:
+        if keep(fc):
+            continue
+        w = tables[fc.embedding_name].weight
+        lo, hi = feature_index[fc.name]
+        if fc.combiner not in ("sum", "mean", "max"):
+            raise ValueError('parameter mode should in [sum, mean, max]')
+        len_col = -1 if fc.length_name is None else feature_index[fc.length_name][0]
+        pooled.append(_FieldSpec(fc.name, w, lo, hi - lo, L.POOL_CODE[fc.combiner], len_col, off))
+        off += int(w.shape[1])
     return fixed, pooled, off
 
 
@@ -364,6 +380,10 @@ class EmbeddingPlan(object):
     column f = wide field f, column ``n_wide`` = the dense half of Linear) and the update reads their gradient in the
     same layout (DCTR_PLAN_WIDE_PER_FIELD, include/dctr.h) -- IFM / DIFM re-weight them per sample before the sum.
 
+    ``unpooled``: True / False for every VarLen deep column, or a collection of column names: those columns become
+    ``maxlen`` fixed fields each (row order: fixed-length fields, un-pooled positions, pooled fields, dense), the others
+    stay pooled.
+
     ``deep_fields``: the deep side as an explicit list of ``(name, table parameter, X column)`` -- fixed-length fields,
     each over the table given -- instead of feature columns over ``deep_tables`` (``deep_columns`` then only supplies the
     dense block).  ``pair`` (needs ``deep_fields``, an even number of one common dim D): fields 2p / 2p+1 are emb1 / emb2
@@ -378,6 +398,10 @@ class EmbeddingPlan(object):
         self.feature_index = feature_index
         self.wide_per_field = bool(wide_per_field)
         self.pair = bool(pair)
+        # names of the VarLen deep columns whose positions the lookup hands out un-pooled (DIN's behaviour sequences)
+        keep = _unpooled_test(unpooled)
+        self.unpooled_columns = tuple(fc.name for fc in split_columns(deep_columns)[1] if keep(fc)) \
+            if deep_tables is not None else ()
         self.n_xcols = max([hi for (_, hi) in feature_index.values()] + [1])
         if deep_fields is not None:
             if deep_tables is not None:
@@ -606,6 +630,7 @@ class EmbeddingPlan(object):
         self.__dict__.setdefault("ld_wide", 1)
         self.__dict__.setdefault("pair", False)
         self.__dict__.setdefault("ld_rows", 0)
+        self.__dict__.setdefault("unpooled_columns", ())
         self._reset_device_image()
 
     # ---- sparse-update mode (see ops.py) ---------------------------------------------------------

@@ -38,6 +38,59 @@ class DNN(nn.Module):
         return h
 
 
+class LocalActivationUnit(nn.Module):
+    """DIN's local activation unit (reference layers/core.py:10-64; same constructor, defaults and ``state_dict`` keys):
+    every behaviour ``k_t`` is scored against the candidate ``q`` by a small MLP on ``[q, k_t, q - k_t, q * k_t]`` and a
+    1-unit ``dense``.  ``forward(query [B, 1, E], user_behavior [B, T, E]) -> [B, T, 1]`` states that formula as torch
+    ops; ``AttentionSequencePoolingLayer`` runs it fused with the mask, the softmax and the weighted sum
+    (``csrc/din.hip``) and reads this module's parameters through ``packed_params``."""
+
+    def __init__(self, hidden_units=(64, 32), embedding_dim=4, activation='sigmoid', dropout_rate=0, dice_dim=3,
+                 l2_reg=0, use_bn=False):
+        super(LocalActivationUnit, self).__init__()
+        self.dnn = DNN(inputs_dim=4 * embedding_dim, hidden_units=hidden_units, activation=activation, l2_reg=l2_reg,
+                       dropout_rate=dropout_rate, dice_dim=dice_dim, use_bn=use_bn)
+        self.dense = nn.Linear(hidden_units[-1], 1)
+
+    def forward(self, query, user_behavior):
+        q = query.expand(-1, user_behavior.size(1), -1)
+        return self.dense(self.dnn(torch.cat([q, user_behavior, q - user_behavior, q * user_behavior], dim=-1)))
+
+    def kernel_activation(self):
+        """The kernel's name for this unit's activation (``_hip/ops.DIN_ACT``) or None when it has none for it, the
+        attention net has BatchNorm layers or dropout is active.  ``'dice'`` is the FROZEN form: the caller may take it
+        only in eval mode and when no gradient is needed."""
+        from .activation import Dice, Identity
+        if self.dnn.use_bn or (self.dnn.dropout_rate > 0 and self.training):
+            return None
+        kinds = set(type(m) for m in self.dnn.activation_layers)
+        if len(kinds) != 1:
+            return None
+        name = {nn.Sigmoid: "sigmoid", nn.ReLU: "relu", Identity: "linear", nn.PReLU: "prelu", Dice: "dice"}.get(kinds.pop())
+        if name == "prelu" and any(m.weight.numel() != 1 for m in self.dnn.activation_layers):
+            return None
+        if name == "dice" and any(m.dim != 3 for m in self.dnn.activation_layers):
+            return None
+        return name
+
+    def packed_params(self, act):
+        """The one vector ``dctr_din_attn_fwd`` reads (include/dctr.h): per hidden layer the weight, the bias and the
+        activation's own -- prelu's slope, or for frozen Dice ``alpha | s | t`` with BatchNorm's running statistics,
+        affine pair and eps folded into ``sigmoid(s * z + t)`` -- then ``dense.weight`` and ``dense.bias``."""
+        parts = []
+        for fc, a in zip(self.dnn.linears, self.dnn.activation_layers):
+            parts += [fc.weight.reshape(-1), fc.bias]
+            if act == "prelu":
+                parts.append(a.weight.reshape(-1))
+            elif act == "dice":
+                bn = a.bn
+                s = (bn.weight if bn.affine else torch.ones_like(bn.running_var)) / torch.sqrt(bn.running_var + bn.eps)
+                t = (bn.bias if bn.affine else torch.zeros_like(bn.running_mean)) - bn.running_mean * s
+                parts += [a.alpha.reshape(-1), s, t]
+        parts += [self.dense.weight.reshape(-1), self.dense.bias]
+        return torch.cat(parts)
+
+
 class PredictionLayer(nn.Module):
     """``sigmoid(logit + bias)`` for task='binary', ``logit + bias`` otherwise
     (reference layers/core.py:137-160)."""

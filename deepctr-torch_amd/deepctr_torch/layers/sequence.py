@@ -48,6 +48,93 @@ class SequencePoolingLayer(nn.Module):
         return total
 
 
+_SOFTMAX_PAD = float(-2 ** 32 + 1)
+
+
+class AttentionSequencePoolingLayer(nn.Module):
+    """DIN's attention pooling (reference layers/sequence.py:80-154; same constructor): every behaviour is weighted by
+    the local activation unit's score against the candidate and the weighted keys are summed.
+
+    ``forward(query [B, 1, E], keys [B, T, E], keys_length [B, 1], mask=None) -> [B, 1, E]`` (``[B, 1, T]`` scores with
+    ``return_score``).  Position t is valid when ``t < keys_length`` or, with ``supports_masking``, where ``mask [B, T]``
+    is set.  Without ``weight_normalization`` an invalid position scores 0; with it, it scores ``-2**32 + 1`` in front of
+    a softmax: weight exactly 0 -- unless the row has no valid position, which then weighs all T keys by 1/T.
+
+    One kernel per direction (``csrc/din.hip``) when the inputs are float32 on the GPU, the shape is inside the kernel's
+    envelope, the activation is linear / relu / sigmoid / prelu (or Dice in eval mode without a gradient: its BatchNorm
+    is then a fixed per-unit affine map), ``return_score`` is off and the attention net has neither BatchNorm layers nor
+    active dropout.  Everything else -- Dice in training, which normalises with the statistics of all B*T rows between
+    the layers -- runs ``_forward_torch``."""
+
+    def __init__(self, att_hidden_units=(80, 40), att_activation='sigmoid', weight_normalization=False,
+                 return_score=False, supports_masking=False, embedding_dim=4, **kwargs):
+        super(AttentionSequencePoolingLayer, self).__init__()
+        from .core import LocalActivationUnit        # (this file also loads on its own, without the package around it)
+        self.return_score = return_score
+        self.weight_normalization = weight_normalization
+        self.supports_masking = supports_masking
+        self.local_att = LocalActivationUnit(hidden_units=att_hidden_units, embedding_dim=embedding_dim,
+                                             activation=att_activation, dropout_rate=0, use_bn=False)
+
+    def _valid(self, keys, keys_length, mask):
+        if self.supports_masking:
+            if mask is None:
+                raise ValueError("When supports_masking=True,input must support masking")
+            return mask.reshape(keys.shape[0], -1).to(torch.bool)
+        return _valid_positions(keys_length, keys.shape[1])
+
+    def kernel_route(self, T, dims, tensors, needs_grad):
+        """The kernel's activation name when the fused route takes this call, else None."""
+        from .._hip import ops as _ops
+        if self.return_score or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return None
+        act = self.local_att.kernel_activation()
+        if act is None or (act == "dice" and (self.training or needs_grad)):
+            return None
+        if self.local_att.dense.weight.dtype != torch.float32:          # (a module is converted as a whole)
+            return None
+        key = (int(T), tuple(dims), act)                                # the envelope: asked of the library once per shape
+        cache = self.__dict__.setdefault("_route_cache", {})
+        if key not in cache:
+            hidden = [fc.out_features for fc in self.local_att.dnn.linears]
+            cache[key] = _ops.din_attention_supported(T, list(dims), hidden, act)
+        return act if cache[key] else None
+
+    def fused(self, Q, K, segs, T, lengths=None, mask=None, act=None):
+        """The kernel on rows that hold the query and key segments (``_hip/ops.DINAttentionFunction``) -> ``[B, E]``"""
+        from .._hip import ops as _ops
+        la = self.local_att
+        params = la.packed_params(act)
+        keep = torch.is_grad_enabled() and (Q.requires_grad or (K is not None and K.requires_grad) or params.requires_grad)
+        hidden = tuple(fc.out_features for fc in la.dnn.linears)
+        return _ops.DINAttentionFunction.apply(Q, K, params, tuple(segs), int(T), hidden, act,
+                                               bool(self.weight_normalization), lengths, mask, keep)
+
+    def forward(self, query, keys, keys_length, mask=None):
+        B, T, E = keys.shape
+        valid = self._valid(keys, keys_length, mask)
+        needs_grad = torch.is_grad_enabled() and (query.requires_grad or keys.requires_grad or
+                                                  any(p.requires_grad for p in self.local_att.parameters()))
+        act = self.kernel_route(T, [E], (query, keys), needs_grad)
+        if act is None:
+            return self._forward_torch(query, keys, valid)
+        if self.supports_masking:
+            lengths, m8 = None, valid.to(torch.uint8).contiguous()
+        else:
+            lengths, m8 = keys_length.reshape(-1).to(torch.int32).contiguous(), None
+        out = self.fused(query.reshape(B, E), keys.reshape(B, T * E), [(E, 0, 0, E)], T, lengths, m8, act)
+        return out.unsqueeze(1)
+
+    def _forward_torch(self, query, keys, valid):
+        """the layer's formula as torch ops: scores, mask, optional softmax, weighted sum"""
+        score = self.local_att(query, keys).transpose(1, 2)                              # [B, 1, T]
+        fill = torch.full_like(score, _SOFTMAX_PAD) if self.weight_normalization else torch.zeros_like(score)
+        score = torch.where(valid.unsqueeze(1), score, fill)
+        if self.weight_normalization:
+            score = torch.softmax(score, dim=-1)
+        return score if self.return_score else torch.matmul(score, keys)
+
+
 class KMaxPooling(nn.Module):
     """The ``k`` largest values along ``axis``, largest first (the layer of reference layers/sequence.py:157-189; same
     constructor, same two ``ValueError`` texts).  ``ConvLayer`` fuses it with the convolution in front of it

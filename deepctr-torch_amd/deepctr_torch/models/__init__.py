@@ -8,6 +8,7 @@ from .dcn import DCN
 from .dcnmix import DCNMix
 from .deepfm import DeepFM
 from .difm import DIFM
+from .din import DIN
 from .fibinet import FiBiNET
 from .ifm import IFM
 from .nfm import NFM
@@ -17,4 +18,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN", "CCPM"]
+           "IFM", "DIFM", "ONN", "CCPM", "DIN"]

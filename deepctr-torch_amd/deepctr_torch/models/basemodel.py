@@ -115,6 +115,8 @@ class Linear(nn.Module):
 class BaseModel(nn.Module):
     # IFM / DIFM: the model plan hands the first-order weights out per field (EmbeddingPlan(wide_per_field=True))
     _wide_per_field = False
+    # DIN: names of the VarLen columns the model plan hands out un-pooled (EmbeddingPlan(unpooled=names))
+    _unpooled_columns = ()
 
     def __init__(self, linear_feature_columns, dnn_feature_columns, l2_reg_linear=1e-5, l2_reg_embedding=1e-5,
                  init_std=0.0001, seed=1024, task='binary', device='cpu', gpus=None):
@@ -207,7 +209,8 @@ class BaseModel(nn.Module):
                                        deep_tables=self.embedding_dict,
                                        wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
                                        wide_dense_weight=getattr(lm, "weight", None),
-                                       wide_per_field=self._wide_per_field)
+                                       wide_per_field=self._wide_per_field,
+                                       unpooled=tuple(self._unpooled_columns) or False)
             object.__setattr__(self.embedding_dict, "_dctr_owner_plan", self._plan)
             object.__setattr__(lm.embedding_dict, "_dctr_owner_plan", self._plan)
             if lm._plan is not None:

@@ -124,6 +124,11 @@ def _refuse_wide_per_field(plan, who):
     if getattr(plan, "pair", False):
         raise NotImplementedError("%s: this model looks its tables up through the pair lookup (ONN); multi-GPU "
                                   "training of this model is not implemented -- train on one GPU" % who)
+    # DIN's behaviour sequences (EmbeddingPlan(unpooled=names)): the row gradient of every position comes out of the
+    # attention kernel's backward, and the trainers' payloads are laid out for pooled VarLen fields
+    if getattr(plan, "unpooled_columns", ()):
+        raise NotImplementedError("%s: this model reads un-pooled behaviour sequences out of its lookup (DIN); "
+                                  "multi-GPU training of this model is not implemented -- train on one GPU" % who)
 
 
 class DataParallelTrainer(object):

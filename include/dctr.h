@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 29
+#define DCTR_ABI_VERSION 30
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -417,6 +417,51 @@ int dctr_ccpm_fwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D,
 int dctr_ccpm_bwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, int32_t n_layers, const int32_t* width,
                   const int32_t* filters, const int32_t* k, const float* params, const uint8_t* sel, const float* g_out,
                   int64_t ld_gout, float* gE, int64_t ld_ge, float* g_params, float* workspace, dctr_stream_t stream);
+
+/* ---- AttentionSequencePoolingLayer of DIN / DIEN (sequence.py:80-154 over core.py:10-64; csrc/din.hip) -----------------
+ * Per sample, with query q [E], keys k_t [E] (t < T), hidden layers l = 1..n_layers of hidden[l-1] units:
+ *   x_t = [q, k_t, q - k_t, q * k_t]   a_0 = x_t   a_l = act(W_l a_{l-1} + b_l)   s_t = dense.w . a_L + dense.b
+ *   softmax == 0:  w_t = s_t on valid positions, 0 elsewhere: an invalid position contributes nothing and gets no gradient
+ *   softmax != 0:  invalid scores are -2^32 + 1 before the softmax: weight exactly 0 whenever one position is valid; a
+ *                  sample WITHOUT a valid position gets w_t = 1/T on all T keys, its key gradient is g / T and nothing
+ *                  flows from it to the scores or the parameters
+ *   out = sum_t w_t k_t.  Invalid positions are never evaluated (every position is independent).
+ * Addressing, n_seg <= 4 segments of dim[j] floats, E = sum_j dim[j] (dim, q_off, k_off, k_step: HOST arrays):
+ *   q(b, j) = Q + b*ld_q + q_off[j]        k(b, t, j) = K + b*ld_k + k_off[j] + t*k_step[j]        out + b*ld_out [E]
+ *   (one contiguous [B, T, E]: n_seg = 1, k_step = E; the model's gathered row: k_step[j] = dim[j], Q == K allowed).
+ * Validity from exactly ONE of len [B] int32 (t valid iff t < len[b]; above T: all, 0 or less: none) and mask [B, T] bytes
+ * (non-zero = valid); the other pointer is NULL.
+ * act: 0 linear, 1 relu, 2 sigmoid, 3 prelu (one slope per layer), 4 frozen Dice, FORWARD ONLY (the backward returns
+ * DCTR_ENOSUP): a = z * (alpha + (1 - alpha) * sigmoid(s*z + t)) per unit, s and t folded from BatchNorm's running
+ * statistics, affine pair and eps.  Dice with batch statistics is not in the kernel.
+ * params, one device vector (g_params likewise): per hidden layer W [H_l, in_l] row-major (in_1 = 4E, in_l = H_{l-1}),
+ * b [H_l], then the activation's own (prelu: slope [1]; Dice: alpha [H_l] | s [H_l] | t [H_l]; else nothing); then
+ * dense.weight [H_L], dense.bias [1].
+ * weights [B, T] (contiguous): the w_t; the forward writes them when the pointer is not NULL, the backward needs them and
+ * recomputes everything else from Q, K and params.  The backward writes every element of every q segment at
+ * gQ + b*ld_gq + q_off[j] and of every k segment at gK + b*ld_gk + k_off[j] + t*k_step[j] (zeros at invalid positions
+ * included), nothing outside the segments, and g_params: fixed-order sums, no atomics, identical bits from run to run.
+ * workspace: dctr_din_attn_bwd_workspace_floats(B, n_params) floats.
+ * DCTR_ENOSUP (dctr_din_attn_supported == 0) unless E <= 64, 1 <= T <= 128 (= DCTR_MAX_UNIT_SLOTS: a model whose history
+ * shares its table with the query column is bounded by T <= 127), n_seg <= 4, 1 <= n_layers <= 3, hidden[l] <= 128.  No
+ * further LDS condition: 32 (forward) / 16 (backward) valid positions are in LDS at a time, which at the largest shape is
+ *   forward   4 * (11 E + 3 T + 1 + 32 (E + 1 + sum_l (H_l + 1)))                                           <= 62.3 KB
+ *   backward  4 * (9 E + 5 T + 1 + 16 (2 E + 1 + sum_l (H_l + 1) + 3 (max_l H_l + 1)) + max_l H_l)         <= 63.2 KB
+ * B == 0 returns DCTR_OK before any buffer check.                                                                          */
+int dctr_din_attn_supported(int32_t T, int32_t n_seg, const int32_t* dim, int32_t n_layers, const int32_t* hidden,
+                            int32_t act);
+size_t dctr_din_attn_bwd_workspace_floats(int32_t B, int32_t n_params);
+int dctr_din_attn_fwd(const float* Q, int64_t ld_q, const float* K, int64_t ld_k, int32_t B, int32_t T, int32_t n_seg,
+                      const int32_t* dim, const int64_t* q_off, const int64_t* k_off, const int64_t* k_step,
+                      const int32_t* len, const uint8_t* mask, int32_t n_layers, const int32_t* hidden, int32_t act,
+                      int32_t softmax, const float* params, float* out, int64_t ld_out, float* weights,
+                      dctr_stream_t stream);
+int dctr_din_attn_bwd(const float* Q, int64_t ld_q, const float* K, int64_t ld_k, int32_t B, int32_t T, int32_t n_seg,
+                      const int32_t* dim, const int64_t* q_off, const int64_t* k_off, const int64_t* k_step,
+                      const int32_t* len, const uint8_t* mask, int32_t n_layers, const int32_t* hidden, int32_t act,
+                      int32_t softmax, const float* params, const float* weights, const float* g_out, int64_t ld_gout,
+                      float* gQ, int64_t ld_gq, float* gK, int64_t ld_gk, float* g_params, float* workspace,
+                      dctr_stream_t stream);
 
 /* ---- InteractingLayer of AutoInt (interaction.py:328-394): multi-head self-attention over the fields (csrc/interact.hip)
  *   Q = E Wq, K = E Wk, V = E Wv;  head n = columns [n*A, (n+1)*A), A = D / H;  P_n = softmax_rows(Q_n K_n^T (/ sqrt(A)
