@@ -9,7 +9,6 @@ scatter executed inside ``EmbedFunction.backward``.  What that scatter does is s
                             it as ``param.grad`` -- bit-for-bit the tensor the reference hands to ANY
                             optimizer / regulariser (default; O(V) only if the optimizer is).
   ``("sgd", lr)``           ``table[row] -= lr * g`` straight from the scatter kernel.
-  ``("sgd2", lr)``          two-pass SGD (needed when a max-pooled field re-reads the table).
   ``("adagrad", lr, eps)``  scatter into ``gacc``, then ``dctr_embed_apply`` consumes the touched rows.
 """
 import contextlib
@@ -213,7 +212,7 @@ def _update_tables(plan, X, ids_t, parts_t, seg_event, g_out, ld_g, out, fm_s, g
             plan.ensure_gacc()
             plan.prepare_dense_grads()
             opt, lr, eps = L.UPD_ACCUM, 0.0, 0.0
-        elif kind in ("sgd", "sgd2"):
+        elif kind == "sgd":
             opt, lr, eps = L.UPD_SGD, float(update[1]), 0.0
         elif kind == "adagrad":
             opt, lr, eps = L.UPD_ADAGRAD, float(update[1]), float(update[2])
@@ -259,7 +258,7 @@ def _update_tables(plan, X, ids_t, parts_t, seg_event, g_out, ld_g, out, fm_s, g
     cplan = plan.bind(X.device)
     L.check(lib.dctr_embed_bwd(cplan, _ptr(X), X.stride(0), B, _ptr(g_out), ld_g, _ptr(out), plan.ld_out,
                                _ptr(g_fm), _ptr(g_wide), L.BWD_ACCUM, 0.0, stream), "dctr_embed_bwd(accum)")
-    if kind in ("sgd", "sgd2"):
+    if kind == "sgd":
         L.check(lib.dctr_embed_apply(cplan, _ptr(X), X.stride(0), B, L.OPT_SGD, float(update[1]), 0.0, stream),
                 "dctr_embed_apply(sgd)")
     elif kind == "adagrad":

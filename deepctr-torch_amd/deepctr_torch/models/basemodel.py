@@ -37,6 +37,7 @@ from .._hip import mlp as _mlp
 from .._hip import ops as _ops
 from .._hip import step as _step
 from .._hip.plan import EmbeddingPlan
+from .._hip.update_paths import match_optimizer, regularizers
 from ..inputs import SparseFeat, VarLenSparseFeat, build_input_features, create_embedding_matrix, split_columns
 from ..layers import PredictionLayer
 from ..layers.utils import slice_arrays
@@ -200,21 +201,24 @@ class BaseModel(nn.Module):
     # ------------------------------------------------------------------------------------------------
     # hot path entry points
     # ------------------------------------------------------------------------------------------------
+    def _build_plan(self):
+        """-> (the model-wide compiled schema, the ModuleDicts whose tables it holds): deep side =
+        ``dnn_feature_columns`` over ``embedding_dict``, wide side = ``linear_feature_columns`` over
+        ``linear_model.embedding_dict``."""
+        lm = self.linear_model
+        plan = EmbeddingPlan(self.feature_index, deep_columns=self.dnn_feature_columns, deep_tables=self.embedding_dict,
+                             wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
+                             wide_dense_weight=getattr(lm, "weight", None), wide_per_field=self._wide_per_field,
+                             unpooled=tuple(self._unpooled_columns) or False)
+        return plan, (self.embedding_dict, lm.embedding_dict)
+
     def model_plan(self):
-        """The model-wide compiled schema: deep side = ``dnn_feature_columns`` over ``embedding_dict``,
-        wide side = ``linear_feature_columns`` over ``linear_model.embedding_dict``."""
         if self._plan is None:
-            lm = self.linear_model
-            self._plan = EmbeddingPlan(self.feature_index, deep_columns=self.dnn_feature_columns,
-                                       deep_tables=self.embedding_dict,
-                                       wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
-                                       wide_dense_weight=getattr(lm, "weight", None),
-                                       wide_per_field=self._wide_per_field,
-                                       unpooled=tuple(self._unpooled_columns) or False)
-            object.__setattr__(self.embedding_dict, "_dctr_owner_plan", self._plan)
-            object.__setattr__(lm.embedding_dict, "_dctr_owner_plan", self._plan)
-            if lm._plan is not None:
-                lm._plan.share_update_with(self._plan)
+            self._plan, owned = self._build_plan()
+            for tables in owned:      # secondary plans over these tables (Linear.plan, gather_columns) share its update
+                object.__setattr__(tables, "_dctr_owner_plan", self._plan)
+            if self.linear_model._plan is not None:
+                self.linear_model._plan.share_update_with(self._plan)
             self._apply_update_mode()
         elif self._plan.update[0] == "lazy" and self._plan._lazy is None:
             self._apply_update_mode()        # an unpickled model: the lazy state is rebuilt from the optimizer
@@ -348,17 +352,13 @@ class BaseModel(nn.Module):
             rv = lazy.reg_value(self.device)
             if rv is not None:
                 total = total + rv
-        for weight_list, l1, l2 in self.regularization_weight:
-            if not (l1 > 0 or l2 > 0):
+        for p, l1, l2 in regularizers(self):
+            if id(p) in lazy_ids:
                 continue
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w  # named_parameters() yields (name, tensor)
-                if id(p) in lazy_ids:
-                    continue
-                if l1 > 0:
-                    total = total + torch.sum(l1 * torch.abs(p))
-                if l2 > 0:
-                    total = total + torch.sum(l2 * torch.square(p))
+            if l1 > 0:
+                total = total + torch.sum(l1 * torch.abs(p))
+            if l2 > 0:
+                total = total + torch.sum(l2 * torch.square(p))
         return total
 
     def add_auxiliary_loss(self, aux_loss, alpha):
@@ -504,117 +504,59 @@ class BaseModel(nn.Module):
     def _embedding_reg_active(self):
         return any((l1 > 0 or l2 > 0) for (_, l1, l2) in self.regularization_weight[:self._n_embedding_reg_groups])
 
-    def _sparse_update_mode(self):
-        """("sgd", lr) / ("adagrad", lr, eps) when the fused O(batch) update is EXACTLY the reference's dense
-        update, otherwise ("dense",)."""
-        opt = getattr(self, "optim", None)
-        if opt is None or self._plan is None or os.environ.get("DCTR_SPARSE_UPDATE", "1") == "0":
-            return ("dense",), {}
-        tables = self._plan.table_params
-        if not tables or self._embedding_reg_active() or not all(p.requires_grad for p in tables):
-            return ("dense",), {}         # (a frozen table: the in-kernel optimizers would move it)
-        group_of = {}
-        for grp in opt.param_groups:
-            for p in grp["params"]:
-                group_of[id(p)] = grp
-        groups = [group_of.get(id(p)) for p in tables]
-        if any(g is None for g in groups):
-            return ("dense",), {}
-        g0 = groups[0]
-
-        def same(key):
-            return all(g.get(key) == g0.get(key) for g in groups)
-
-        if type(opt) is torch.optim.SGD:
-            ok = same("lr") and all(g.get("momentum", 0) == 0 and g.get("weight_decay", 0) == 0 and
-                                    not g.get("nesterov", False) and not g.get("maximize", False) for g in groups)
-            if ok:
-                return ("sgd", float(g0["lr"])), {}
-        if type(opt) is torch.optim.Adagrad:
-            ok = same("lr") and same("eps") and all(g.get("lr_decay", 0) == 0 and g.get("weight_decay", 0) == 0 and
-                                                    not g.get("maximize", False) for g in groups)
-            if ok and all("sum" in opt.state.get(p, {}) for p in tables):
-                return ("adagrad", float(g0["lr"]), float(g0["eps"])), {p: opt.state[p]["sum"] for p in tables}
-        return ("dense",), {}
-
-    def _lazy_update_mode(self):
-        """("lazy", kind) + the LazyState arguments when the tables can take the EXACT lazy form of the reference's
-        dense regularised / Adam / RMSprop update (csrc/lazy.hip): fixed-length fields over distinct tables, a plain SGD /
-        Adagrad / Adam / RMSprop over all tables, L2-only regularisation of the tables.  None otherwise."""
-        opt = getattr(self, "optim", None)
-        plan = self._plan
-        if opt is None or plan is None or os.environ.get("DCTR_LAZY_UPDATE", "1") == "0" or \
-                os.environ.get("DCTR_SPARSE_UPDATE", "1") == "0" or getattr(self, "_no_lazy_update", False):
-            return None
+    def _table_update_mode(self):
+        """What ``backward`` does to the tables, and its state.  ``("sgd", lr)`` / ``("adagrad", lr, eps)`` + the tables'
+        ``sum`` when the fused O(batch) update is EXACTLY the reference's dense update: a plain SGD / Adagrad over all
+        tables, no regulariser on them.  ``("lazy", kind)`` + the LazyState arguments when they can take the EXACT lazy
+        form of the reference's dense regularised / Adam / RMSprop update (csrc/lazy.hip): fixed-length fields over
+        distinct tables, L2-only regularisation of the tables.  Otherwise ``("dense",)``."""
+        plan, opt = self._plan, getattr(self, "optim", None)
         tables = plan.table_params
-        if not tables or not plan.simple_units or plan.max_dim > 64 * (4 if plan.vec == 4 else 1) or \
-                not all(p.requires_grad for p in tables):
-            return None
+        dense = (("dense",), {})
+        if os.environ.get("DCTR_SPARSE_UPDATE", "1") == "0" or not all(p.requires_grad for p in tables):
+            return dense                  # (a frozen table: the in-kernel optimizers would move it)
+        m = match_optimizer(opt, tables)
+        if m is None:
+            return dense
+        kind = m[0]
+        if kind in ("sgd", "adagrad") and not self._embedding_reg_active():
+            return m, ({p: opt.state[p]["sum"] for p in tables} if kind == "adagrad" else {})
+        if os.environ.get("DCTR_LAZY_UPDATE", "1") == "0" or getattr(self, "_no_lazy_update", False) or \
+                not plan.simple_units or plan.max_dim > 64 * (4 if plan.vec == 4 else 1):
+            return dense
         l2 = {}
         tids = set(id(p) for p in tables)
-        for weight_list, l1, l2v in self.regularization_weight:
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                if id(p) in tids:
-                    if l1 > 0:
-                        return None
-                    l2[p] = l2.get(p, 0.0) + float(l2v)
-        group_of = {}
-        for grp in opt.param_groups:
-            for p in grp["params"]:
-                group_of[id(p)] = grp
-        groups = [group_of.get(id(p)) for p in tables]
-        if any(g is None for g in groups):
-            return None
-        g0 = groups[0]
+        for p, l1, l2v in regularizers(self):
+            if id(p) in tids:
+                if l1 > 0:
+                    return dense
+                l2[p] = l2.get(p, 0.0) + float(l2v)
 
-        def same(key):
-            return all(g.get(key) == g0.get(key) for g in groups)
+        def moment(key):
+            for p in tables:      # torch creates RMSprop's / Adam's state at the first step(); the kernels need it now
+                st = opt.state[p]
+                if key not in st:
+                    st.setdefault("step", torch.tensor(0.0, dtype=torch.float32))
+                    st[key] = torch.zeros_like(p.data)
+            return {p: opt.state[p][key] for p in tables}
 
-        plain = all(g.get("weight_decay", 0) == 0 and not g.get("maximize", False) for g in groups)
-        if not plain or not same("lr"):
-            return None
-        if type(opt) is torch.optim.SGD:
-            if all(g.get("momentum", 0) == 0 and not g.get("nesterov", False) for g in groups):
-                return dict(kind="sgd", lr=g0["lr"], eps=0.0, beta1=0.0, beta2=0.0, l2=l2, s1={}, s2={})
-        if type(opt) is torch.optim.Adagrad:
-            if same("eps") and all(g.get("lr_decay", 0) == 0 for g in groups) and \
-                    all("sum" in opt.state.get(p, {}) for p in tables):
-                return dict(kind="adagrad", lr=g0["lr"], eps=g0["eps"], beta1=0.0, beta2=0.0, l2=l2,
-                            s1={p: opt.state[p]["sum"] for p in tables}, s2={})
-        if type(opt) is torch.optim.RMSprop:
-            if same("eps") and same("alpha") and all(g.get("momentum", 0) == 0 and not g.get("centered", False) and
-                                                       not g.get("capturable", False) for g in groups):
-                for p in tables:      # torch creates the state at the first step(); the kernels need it now
-                    st = opt.state[p]
-                    if "square_avg" not in st:
-                        st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                        st["square_avg"] = torch.zeros_like(p.data)
-                # (beta1 carries 1 - alpha, rounded from double like the scalar torch hands its kernels)
-                return dict(kind="rmsprop", lr=g0["lr"], eps=g0["eps"], beta1=1 - g0["alpha"], beta2=g0["alpha"], l2=l2,
-                            s1={p: opt.state[p]["square_avg"] for p in tables}, s2={})
-        if type(opt) is torch.optim.Adam:
-            if same("eps") and same("betas") and all(not g.get("amsgrad", False) and not g.get("capturable", False) and
-                                                       not g.get("fused", False) for g in groups):
-                for p in tables:      # torch creates Adam's state at the first step(); the kernels need it now
-                    st = opt.state[p]
-                    if "exp_avg" not in st:
-                        st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                        st["exp_avg"] = torch.zeros_like(p.data)
-                        st["exp_avg_sq"] = torch.zeros_like(p.data)
-                return dict(kind="adam", lr=g0["lr"], eps=g0["eps"], beta1=g0["betas"][0], beta2=g0["betas"][1], l2=l2,
-                            s1={p: opt.state[p]["exp_avg"] for p in tables},
-                            s2={p: opt.state[p]["exp_avg_sq"] for p in tables})
-        return None
+        lazy = dict(kind=kind, lr=m[1], eps=0.0, beta1=0.0, beta2=0.0, l2=l2, s1={}, s2={})
+        if kind == "adagrad":
+            lazy.update(eps=m[2], s1=moment("sum"))
+        elif kind == "rmsprop":
+            # (beta1 carries 1 - alpha, rounded from double like the scalar torch hands its kernels)
+            lazy.update(eps=m[2], beta1=1 - m[3], beta2=m[3], s1=moment("square_avg"))
+        elif kind == "adam":
+            lazy.update(eps=m[2], beta1=m[3], beta2=m[4], s1=moment("exp_avg"), s2=moment("exp_avg_sq"))
+        return ("lazy", kind), lazy
 
     def _apply_update_mode(self):
         if self._plan is None:
             return
-        mode, state = self._sparse_update_mode()
-        lazy = self._lazy_update_mode() if mode[0] == "dense" else None
-        if lazy is not None:
+        mode, state = self._table_update_mode()
+        if mode[0] == "lazy":
             from .._hip.plan import LazyState
-            new = LazyState(self._plan, optimizer=self.optim, **lazy)
+            new = LazyState(self._plan, optimizer=self.optim, **state)
             old = self._plan._lazy
             if old is not None and old.signature() == new.signature() and old.optimizer is self.optim:
                 old.s1, old.s2 = new.s1, new.s2       # same schedule: keep the stamps and the step counter
@@ -625,7 +567,7 @@ class BaseModel(nn.Module):
                 self._plan._lazy = new
             self._plan.set_state({})
             self._plan.ensure_gacc()
-            self._plan.update = ("lazy", lazy["kind"])
+            self._plan.update = mode
             return
         if self._plan._lazy is not None:
             self._plan._lazy.flush()
@@ -682,38 +624,10 @@ class BaseModel(nn.Module):
     # fused train step: tower + head + dense optimizer on the C-ABI kernels (launch count)
     # ------------------------------------------------------------------------------------------------
     def _dense_update_mode(self, params):
-        """("sgd", lr) / ("adagrad", lr, eps) when one fused pass over the dense slab is EXACTLY what the
-        compiled torch optimizer would do to ``params``, else None."""
-        opt = getattr(self, "optim", None)
-        if opt is None or not params:
-            return None
-        group_of = {}
-        for grp in opt.param_groups:
-            for p in grp["params"]:
-                group_of[id(p)] = grp
-        groups = [group_of.get(id(p)) for p in params]
-        if any(g is None for g in groups):
-            return None
-        g0 = groups[0]
-
-        def same(key):
-            return all(g.get(key) == g0.get(key) for g in groups)
-
-        if type(opt) is torch.optim.SGD:
-            if same("lr") and all(g.get("momentum", 0) == 0 and g.get("weight_decay", 0) == 0 and
-                                  not g.get("nesterov", False) and not g.get("maximize", False) for g in groups):
-                return ("sgd", float(g0["lr"]))
-        if type(opt) is torch.optim.Adagrad:
-            if same("lr") and same("eps") and all(g.get("lr_decay", 0) == 0 and g.get("weight_decay", 0) == 0 and
-                                                  not g.get("maximize", False) for g in groups) and \
-                    all("sum" in opt.state.get(p, {}) for p in params):
-                return ("adagrad", float(g0["lr"]), float(g0["eps"]))
-        if type(opt) is torch.optim.Adam:
-            if same("lr") and same("eps") and same("betas") and \
-                    all(g.get("weight_decay", 0) == 0 and not g.get("maximize", False) and not g.get("amsgrad", False)
-                        and not g.get("capturable", False) and not g.get("fused", False) for g in groups):
-                return ("adam", float(g0["lr"]), float(g0["eps"]), float(g0["betas"][0]), float(g0["betas"][1]))
-        return None
+        """("sgd", lr) / ("adagrad", lr, eps) / ("adam", lr, eps, beta1, beta2) when one fused pass over the dense slab
+        is EXACTLY what the compiled torch optimizer would do to ``params``, else None."""
+        m = match_optimizer(getattr(self, "optim", None), params)
+        return m if m is not None and m[0] != "rmsprop" else None
 
     def _fused_step_state(self):
         """The fused train step applies when every piece of the step is one of our kernels: binary task with
@@ -745,18 +659,16 @@ class BaseModel(nn.Module):
         # applied inside the slab optimizer kernel (DenseSlab.set_l2) -- never as dense autograd nodes
         table_ids = set(id(p) for p in plan.table_params)
         lam_of = {}
-        for weight_list, l1, l2 in self.regularization_weight:
-            if not (l1 > 0 or l2 > 0):
+        for p, l1, l2 in regularizers(self):
+            if l1 > 0:
+                return None
+            if not l2 > 0:
                 continue
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                if l1 > 0:
+            if id(p) in table_ids:
+                if plan.update[0] != "lazy":
                     return None
-                if id(p) in table_ids:
-                    if plan.update[0] != "lazy":
-                        return None
-                else:
-                    lam_of[p] = lam_of.get(p, 0.0) + float(l2)
+            else:
+                lam_of[p] = lam_of.get(p, 0.0) + float(l2)
         if getattr(dnn, "dropout_rate", 0):     # the fused step is cached across train() / eval() switches
             return None
         spec = _mlp.tower_layers(dnn, dnn_linear)
@@ -915,17 +827,13 @@ class BaseModel(nn.Module):
                 stacked.update(id(w) for w in sw[0])
         known = set(id(p) for p in every)
         out = {}
-        for weight_list, l1, l2 in self.regularization_weight:
-            if not (l1 > 0 or l2 > 0):
+        for p, l1, l2 in regularizers(self):
+            if not (l1 > 0 or l2 > 0) or id(p) in lazy_ids:
                 continue
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                if id(p) in lazy_ids:
-                    continue
-                if l1 > 0 or id(p) in out or id(p) in stacked or id(p) not in known or not p.is_cuda or \
-                        p.dtype != torch.float32 or not p.is_contiguous() or not p.requires_grad:
-                    return None
-                out[id(p)] = (p, float(l2))
+            if l1 > 0 or id(p) in out or id(p) in stacked or id(p) not in known or not p.is_cuda or \
+                    p.dtype != torch.float32 or not p.is_contiguous() or not p.requires_grad:
+                return None
+            out[id(p)] = (p, float(l2))
         return out
 
     def _bce_head_ok(self, xb):
@@ -950,7 +858,7 @@ class BaseModel(nn.Module):
         regularised table): the logged total loss is then the loss itself and three launches are saved."""
         if self._plan is not None and self._plan.update[0] == "lazy":
             return True
-        return any((l1 > 0 or l2 > 0) and len(weight_list) > 0 for weight_list, l1, l2 in self.regularization_weight)
+        return any(l1 > 0 or l2 > 0 for _, l1, l2 in regularizers(self))
 
     def _step_dense_multi(self, l2map=None):
         """One ``dctr_dense_opt_multi`` launch for every dense parameter autograd left a gradient on, when the compiled

@@ -76,27 +76,21 @@ class ONN(BaseModel):
         self.add_regularization_weight(self.dnn_linear.weight, l2=l2_reg_dnn)
         self.to(device)
 
-    def model_plan(self):
+    def _build_plan(self):
         """The PAIR plan: deep side = ``emb1`` / ``emb2`` of every pair (fields 2p / 2p + 1, reference pair order) over
         the X columns of the pair's two features, wide side = ``linear_feature_columns`` as for every model.  Its tables --
-        the pair tables and the first-order tables -- are what the sparse / lazy update modes see."""
-        if self._plan is None:
-            lm = self.linear_model
-            fields = []
-            for a, b in self._pair_columns:
-                mod = self.second_order_embedding_dict[a + "+" + b]
-                fields.append((a + "+" + b + ".emb1", mod.emb1.weight, self.feature_index[a][0]))
-                fields.append((a + "+" + b + ".emb2", mod.emb2.weight, self.feature_index[b][0]))
-            self._plan = EmbeddingPlan(self.feature_index, deep_columns=self.dnn_feature_columns, deep_fields=fields,
-                                       wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
-                                       wide_dense_weight=getattr(lm, "weight", None), pair=True)
-            object.__setattr__(lm.embedding_dict, "_dctr_owner_plan", self._plan)
-            if lm._plan is not None:
-                lm._plan.share_update_with(self._plan)
-            self._apply_update_mode()
-        elif self._plan.update[0] == "lazy" and self._plan._lazy is None:
-            self._apply_update_mode()        # an unpickled model: the lazy state is rebuilt from the optimizer
-        return self._plan
+        the pair tables and the first-order tables -- are what the update paths see; of the ModuleDicts only the first-order
+        one holds tables of it (``embedding_dict`` is never looked up)."""
+        lm = self.linear_model
+        fields = []
+        for a, b in self._pair_columns:
+            mod = self.second_order_embedding_dict[a + "+" + b]
+            fields.append((a + "+" + b + ".emb1", mod.emb1.weight, self.feature_index[a][0]))
+            fields.append((a + "+" + b + ".emb2", mod.emb2.weight, self.feature_index[b][0]))
+        plan = EmbeddingPlan(self.feature_index, deep_columns=self.dnn_feature_columns, deep_fields=fields,
+                             wide_columns=self._linear_feature_columns, wide_tables=lm.embedding_dict,
+                             wide_dense_weight=getattr(lm, "weight", None), pair=True)
+        return plan, (lm.embedding_dict,)
 
     def logit_parts(self, X):
         plan = self.model_plan()

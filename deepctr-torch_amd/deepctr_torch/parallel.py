@@ -27,6 +27,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from ._hip.update_paths import regularizers
+
 
 def _broadcast(t, src, group):
     """dist.broadcast that also serves strided views (tables seated in an interleaved slab, _hip/layout.py):
@@ -187,21 +189,19 @@ class DataParallelTrainer(object):
         tables = set(id(p) for p in self.plan.table_params)
         dense = torch.zeros((1,), device=model.device)
         tab = torch.zeros((1,), device=model.device)
-        for weight_list, l1, l2 in model.regularization_weight:
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                term = None
-                if l1 > 0:
-                    term = torch.sum(l1 * torch.abs(p))
-                if l2 > 0:
-                    t2 = torch.sum(l2 * torch.square(p))
-                    term = t2 if term is None else term + t2
-                if term is None:
-                    continue
-                if id(p) in tables:
-                    tab = tab + term
-                else:
-                    dense = dense + term
+        for p, l1, l2 in regularizers(model):
+            term = None
+            if l1 > 0:
+                term = torch.sum(l1 * torch.abs(p))
+            if l2 > 0:
+                t2 = torch.sum(l2 * torch.square(p))
+                term = t2 if term is None else term + t2
+            if term is None:
+                continue
+            if id(p) in tables:
+                tab = tab + term
+            else:
+                dense = dense + term
         return dense, tab
 
     def _regularization_terms_lazy(self):
@@ -210,15 +210,13 @@ class DataParallelTrainer(object):
         model = self.model
         tables = set(id(p) for p in self.plan.table_params)
         dense = torch.zeros((1,), device=model.device)
-        for weight_list, l1, l2 in model.regularization_weight:
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                if id(p) in tables:
-                    continue
-                if l1 > 0:
-                    dense = dense + torch.sum(l1 * torch.abs(p))
-                if l2 > 0:
-                    dense = dense + torch.sum(l2 * torch.square(p))
+        for p, l1, l2 in regularizers(model):
+            if id(p) in tables:
+                continue
+            if l1 > 0:
+                dense = dense + torch.sum(l1 * torch.abs(p))
+            if l2 > 0:
+                dense = dense + torch.sum(l2 * torch.square(p))
         rv = self.plan.lazy.reg_value(model.device)
         tab = rv.detach() if rv is not None else torch.zeros((1,), device=model.device)
         return dense, tab
@@ -282,7 +280,7 @@ class DataParallelTrainer(object):
                 plan.ensure_gacc()
                 plan.prepare_dense_grads()
                 opt, lr, eps = L.UPD_ACCUM, 0.0, 0.0
-            elif kind in ("sgd", "sgd2"):
+            elif kind == "sgd":
                 opt, lr, eps = L.UPD_SGD, float(plan.update[1]), 0.0
             else:
                 opt, lr, eps = L.UPD_ADAGRAD, float(plan.update[1]), float(plan.update[2])
@@ -603,7 +601,7 @@ class HipShardOps(object):
             return
         NB, dev = grads_all.shape[0], grads_all.device
         kind = plan.update[0]
-        if kind in ("sgd", "sgd2"):
+        if kind == "sgd":
             opt, lr, eps = L.UPD_SGD, float(plan.update[1]), 0.0
         elif kind == "adagrad":
             opt, lr, eps = L.UPD_ADAGRAD, float(plan.update[1]), float(plan.update[2])

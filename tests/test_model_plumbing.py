@@ -62,7 +62,7 @@ def test_in_kernel_optimizer_trajectory(mock, name, opt):
     if plan.table_params:
         # ("lazy", opt): DCNMix keeps the reference's quirk of regularising the linear tables with BaseModel's default
         # 1e-5 whatever l2_reg_linear says (dcnmix.py:52-54 does not forward it) -- the exact lazy form applies
-        assert plan.update[0] in (opt, "sgd2", "lazy")
+        assert plan.update[0] in (opt, "lazy")
         if plan.unit_path and plan.update[0] == opt:
             assert "embed_update:%d" % (0 if opt == "sgd" else 1) in mock.calls
     np.testing.assert_allclose(losses, g["extra"][opt + "3_loss"], rtol=5e-5)
