@@ -60,9 +60,20 @@ def _bilinear_ref(X, Ws, btype):
 
 
 @pytest.mark.parametrize("btype", ["interaction", "each", "all"])
-@pytest.mark.parametrize("B,F,D", [(7, 3, 4), (33, 5, 8), (48, 10, 16), (100, 26, 16), (16, 4, 5), (257, 7, 16)])
+@pytest.mark.parametrize("B,F,D", [(7, 3, 4), (33, 5, 8), (48, 10, 16), (100, 26, 16), (16, 4, 5), (257, 7, 16),
+                                   # F - 1 divisible by none of 5, 4, 3, 2: the backward's ring depth 1 (DCTR_OWN(1))
+                                   (9, 2, 4), (20, 8, 8), (20, 12, 16),
+                                   # the weight kernel with more than one tile per group and idle groups, whose slabs the
+                                   # launcher has to clear: 33 tiles on 32 groups (2 each, 15 groups idle); 65 tiles on
+                                   # 256 / 11 = 23 groups (3 each, the last group idle)
+                                   (520, 5, 8), (1040, 26, 16),
+                                   # the older "tournament" data kernel: with F = 85, D = 4 the owner kernel would need
+                                   # 2 * 16 * 368 * 4 + 4352 + 85 * 84 * 16 = 165 696 B > 158 KB of LDS (F = 84: 158 912 B,
+                                   # which still fits), so 85 is the smallest F at D = 4 that takes that branch
+                                   (20, 85, 4)])
 def test_bilinear_single_input(B, F, D, btype):
     from deepctr_torch.layers import BilinearInteraction
+    assert BilinearInteraction._kernel_fits(F, D)          # (on the kernels, not on the PyTorch-ROCm route)
     torch.manual_seed(F * 31 + D)
     layer = BilinearInteraction(F, D, btype, device=DEV)
     for p in layer.parameters():
@@ -81,6 +92,52 @@ def test_bilinear_single_input(B, F, D, btype):
     _close(X.grad, gX, "gX")
     for k, p in layer.named_parameters():
         _close(p.grad, grads.get("bl." + k), "g" + k)      # ('each': the last field's matrix is never a left factor)
+    # fixed-order sums: a second run gives the same bits
+    first = [X.grad.clone()] + [None if p.grad is None else p.grad.clone() for p in layer.parameters()]
+    X.grad = None
+    for p in layer.parameters():
+        p.grad = None
+    (layer(X) * R).sum().backward()
+    for a, b in zip(first, [X.grad] + [p.grad for p in layer.parameters()]):
+        assert (a is None and b is None) or torch.equal(a, b)
+
+
+@pytest.mark.parametrize("B,F,D", [(520, 5, 8), (1040, 26, 16), (100, 26, 16)])
+def test_bilinear_bwd_on_a_dirty_workspace(B, F, D):
+    """dctr_bilinear_bwd called directly, with the layer's own tables, on a workspace full of 777 and then of NaN.  At
+    (520, 5, 8) and (1040, 26, 16) some groups of the weight kernel have no tile inside the batch, and k_bilinear_reduce_w
+    still adds their slabs: between the launcher's hipMemsetAsync and the zero accumulators such a group stores, nothing of
+    the workspace's old contents may reach gW (through the layer the workspace is a fresh torch.empty, usually zero already:
+    the layer-level test above cannot tell).  (100, 26, 16): 7 groups of one tile each, the branch without the clear."""
+    import ctypes
+    from deepctr_torch._hip import lib as L
+    from deepctr_torch._hip import ops
+    lib, stream = L.lib(), L.stream_handle(torch.device(DEV))
+    meta = ops.BilinearMeta(F, "interaction")
+    sched, pair_w, by_k = meta.device_tables(torch.device(DEV))
+    P = F * (F - 1) // 2
+    torch.manual_seed(B + F)
+    X, R = torch.randn(B, F, D, device=DEV), torch.randn(B, P, D, device=DEV)
+    Wf = torch.randn(meta.n_w, D, D, device=DEV) * 0.3
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    got = []
+    for fill in (777.0, float("nan")):
+        gE = torch.full((B, F, D), 777.0, device=DEV)
+        gW = torch.full((meta.n_w, D, D), 777.0, device=DEV)
+        ws = torch.full((max(1, lib.dctr_bilinear_bwd_workspace_floats(B, P, D)),), fill, device=DEV)
+        rc = lib.dctr_bilinear_bwd(ptr(X), F * D, None, 0, ptr(Wf), ptr(sched), meta.n_sched, meta.slots, ptr(pair_w),
+                                   meta.n_w, P, F, D, B, ptr(R), P * D, ptr(gE), None, ptr(gW), ptr(ws), ptr(by_k),
+                                   by_k.shape[0], stream)
+        torch.cuda.synchronize()
+        assert rc == 0
+        got.append((gE, gW))
+    Pn = {"bl.bilinear.%d.weight" % k: _n(Wf[k]) for k in range(P)}
+    grads = {}
+    gX = O.bilinear_backward(_n(R), _n(X), Pn, "bl.", "interaction", grads)
+    for gE, gW in got:
+        _close(gE, gX, "gE")
+        _close(gW, np.stack([grads["bl.bilinear.%d.weight" % k] for k in range(P)]), "gW")
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
 
 
 @pytest.mark.parametrize("btype", ["interaction", "each", "all"])
@@ -152,7 +209,8 @@ def test_inner_product(B, F, D, reduce_sum):
 
 
 @pytest.mark.parametrize("param", ["vector", "matrix"])
-@pytest.mark.parametrize("B,W,L", [(3, 5, 1), (48, 69, 3), (100, 429, 2), (1000, 429, 2), (7, 845, 4)])
+# (1025, 200, 2): two samples per wave in the vector backward; for `matrix`, 1025 is no multiple of the 16-sample tile
+@pytest.mark.parametrize("B,W,L", [(3, 5, 1), (48, 69, 3), (100, 429, 2), (1000, 429, 2), (7, 845, 4), (1025, 200, 2)])
 def test_crossnet(B, W, L, param):
     from deepctr_torch.layers import CrossNet
     torch.manual_seed(W)
