@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -89,6 +89,18 @@ class DenseItem(ctypes.Structure):
     """``dctr_dense_item_t`` (include/dctr.h): one tensor of a ``dctr_dense_opt_multi`` list."""
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("state", ctypes.c_void_p), ("n", ctypes.c_int64),
                 ("l2", ctypes.c_float), ("pad_", ctypes.c_float)]
+
+
+GATE_MAX_GATES, GATE_MAX_MEMBERS, GATE_MAX_POOL, GATE_MAX_WIDTH = 8, 16, 32, 1152
+
+
+class Gate(ctypes.Structure):
+    """``dctr_gate_t`` (include/dctr.h): one gate of a ``dctr_gate_mix_fwd / _bwd`` call."""
+    _fields_ = [("h", ctypes.c_void_p), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("g_out", ctypes.c_void_p), ("g_h", ctypes.c_void_p), ("gW", ctypes.c_void_p),
+                ("ld_h", ctypes.c_int64), ("ld_w", ctypes.c_int64), ("ld_out", ctypes.c_int64),
+                ("ld_gout", ctypes.c_int64), ("ld_gh", ctypes.c_int64), ("H", ctypes.c_int32), ("n", ctypes.c_int32),
+                ("member", ctypes.c_int32 * GATE_MAX_MEMBERS)]
 
 
 PLAN_HAS_GACC, PLAN_HAS_STATE, PLAN_HAS_MAXPOOL, PLAN_WIDE_PER_FIELD = 1, 2, 4, 8
@@ -255,6 +267,11 @@ SIGNATURES = {
                                          _P, _P, _I64, _P, _P]),
     "dctr_din_attn_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32,
                                          _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "dctr_sizeof_gate": (ctypes.c_size_t, []),
+    "dctr_gate_mix_supported": (ctypes.c_int, [_I32, _I32, _I32, _P, _P]),
+    "dctr_gate_mix_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32, _P, _P]),
+    "dctr_gate_mix_fwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P]),
+    "dctr_gate_mix_bwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "dctr_bi_pooling_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "dctr_bi_pooling_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P]),
 }
@@ -310,7 +327,8 @@ def lib():
                 or handle.dctr_sizeof_lazy_unit() != ctypes.sizeof(LazyUnit) \
                 or handle.dctr_sizeof_lazy_opt() != ctypes.sizeof(LazyOpt) \
                 or handle.dctr_sizeof_dense_step() != ctypes.sizeof(DenseStep) \
-                or handle.dctr_sizeof_dense_item() != ctypes.sizeof(DenseItem):
+                or handle.dctr_sizeof_dense_item() != ctypes.sizeof(DenseItem) \
+                or handle.dctr_sizeof_gate() != ctypes.sizeof(Gate):
             raise RuntimeError("dctr_field_t / dctr_plan_t / dctr_mlp_t layout mismatch between header and binding")
         _lib = handle
     return _lib

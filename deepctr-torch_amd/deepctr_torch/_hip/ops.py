@@ -1523,3 +1523,151 @@ class CrossNetMixFunction(torch.autograd.Function):
         gU = gW3[:, :, :ER].reshape(Lc, W, E, R).permute(0, 2, 1, 3)
         sU, sV, sC, sG, sb = ctx.shapes
         return gX[:, :W], gU.reshape(sU), gV.reshape(sV), gC.reshape(sC), gG.reshape(sG), gb.reshape(sb)
+
+
+# ---- gate mix of the multi-task models (models/multitask; csrc/gate_mix.hip) -------------------------------------------
+def _mix_rows(t):
+    """(2-D float32 tensor with unit inner stride, its row stride): a row-strided view is used in place."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+class _MixMeta(object):
+    """Static description of one gate-mix call (kept out of autograd's tensor arguments)."""
+
+    def __init__(self, P, members, keep):
+        self.P, self.members, self.keep = int(P), tuple(tuple(int(e) for e in m) for m in members), bool(keep)
+
+
+def _mix_call(fn, xs, P, dim, B, gates, extra, dev, what):
+    xp = (ctypes.c_void_p * P)(*[t.data_ptr() for t, _ in xs])
+    xl = (ctypes.c_int64 * P)(*[ld for _, ld in xs])
+    L.check(fn(xp, xl, P, dim, B, gates, len(gates), *(extra + (L.stream_handle(dev),))), what)
+
+
+class GateMixFunction(torch.autograd.Function):
+    """``(meta, x_0 .. x_{P-1}, h_0 .. h_{G-1}, W_0 .. W_{G-1}) -> (out_0 .. out_{G-1})``: every gate over one pool of
+    expert outputs as one launch per direction (``dctr_gate_mix_fwd / _bwd``).  A gate whose output nothing used gets
+    ``None`` for its input and weight gradients, as autograd leaves them in the reference."""
+
+    @staticmethod
+    def forward(ctx, meta, *tensors):
+        lib = L.lib()
+        P, G = meta.P, len(meta.members)
+        L.require_gpu(tensors[0], "expert output")
+        xs = [_mix_rows(t.detach()) for t in tensors[:P]]
+        hs = [_mix_rows(t.detach()) for t in tensors[P:P + G]]
+        Ws = [_mix_rows(t.detach()) for t in tensors[P + G:]]
+        B, dim = xs[0][0].shape
+        dev = xs[0][0].device
+        ld_o = (dim + 3) // 4 * 4          # (a later tower reads the view in place: 16-byte rows)
+        outs = [torch.empty((B, ld_o), dtype=torch.float32, device=dev) for _ in range(G)]
+        ws = [torch.empty((B, len(m)), dtype=torch.float32, device=dev) if meta.keep else None for m in meta.members]
+        gates = (L.Gate * G)()
+        for g in range(G):
+            (h, ldh), (W, ldw), q = hs[g], Ws[g], gates[g]
+            q.h, q.ld_h, q.H = h.data_ptr(), ldh, h.shape[1]
+            q.W, q.ld_w, q.n = W.data_ptr(), ldw, len(meta.members[g])
+            q.out, q.ld_out = outs[g].data_ptr(), ld_o
+            q.w = ws[g].data_ptr() if ws[g] is not None else None
+            for j, e in enumerate(meta.members[g]):
+                q.member[j] = e
+        _mix_call(lib.dctr_gate_mix_fwd, xs, P, dim, B, gates, (), dev, "dctr_gate_mix_fwd")
+        ctx.meta = meta
+        if meta.keep:
+            ctx.save_for_backward(*([t for t, _ in xs] + [t for t, _ in hs] + [t for t, _ in Ws] + ws))
+        ctx.set_materialize_grads(False)
+        return tuple(o[:, :dim] if ld_o != dim else o for o in outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        lib = L.lib()
+        meta = ctx.meta
+        P, G = meta.P, len(meta.members)
+        if all(g is None for g in gouts):
+            return (None,) * (1 + P + 2 * G)
+        saved = ctx.saved_tensors
+        xs = [_mix_rows(t) for t in saved[:P]]
+        hs = [_mix_rows(t) for t in saved[P:P + G]]
+        Ws = [_mix_rows(t) for t in saved[P + G:P + 2 * G]]
+        ws = saved[P + 2 * G:]
+        B, dim = xs[0][0].shape
+        dev = xs[0][0].device
+        gos = [None if g is None else _mix_rows(g) for g in gouts]
+        gxs = [torch.empty((B, dim), dtype=torch.float32, device=dev) for _ in range(P)]
+        ghs = [torch.empty((B, h.shape[1]), dtype=torch.float32, device=dev) for h, _ in hs]
+        gWs = [(torch.empty if B else torch.zeros)((W.shape[0], ldw), dtype=torch.float32, device=dev) for W, ldw in Ws]
+        gates = (L.Gate * G)()
+        for g in range(G):
+            (h, ldh), (W, ldw), q = hs[g], Ws[g], gates[g]
+            q.h, q.ld_h, q.H = h.data_ptr(), ldh, h.shape[1]
+            q.W, q.ld_w, q.n = W.data_ptr(), ldw, len(meta.members[g])
+            q.w = ws[g].data_ptr()
+            if gos[g] is not None:
+                q.g_out, q.ld_gout = gos[g][0].data_ptr(), gos[g][1]
+            q.g_h, q.ld_gh, q.gW = ghs[g].data_ptr(), max(1, h.shape[1]), gWs[g].data_ptr()
+            for j, e in enumerate(meta.members[g]):
+                q.member[j] = e
+        ns, lds = _i32s([len(m) for m in meta.members]), _i32s([ldw for _, ldw in Ws])
+        work = torch.empty((max(1, lib.dctr_gate_mix_bwd_workspace_floats(B, G, ns, lds)),), dtype=torch.float32,
+                           device=dev)
+        gp = (ctypes.c_void_p * P)(*[t.data_ptr() for t in gxs])
+        gl = (ctypes.c_int64 * P)(*[dim] * P)
+        _mix_call(lib.dctr_gate_mix_bwd, xs, P, dim, B, gates, (gp, gl, _ptr(work)), dev, "dctr_gate_mix_bwd")
+        live = [g is not None for g in gos]
+        ret_h = [ghs[g] if live[g] else None for g in range(G)]
+        ret_W = [(gWs[g][:, :Ws[g][0].shape[1]] if Ws[g][1] != Ws[g][0].shape[1] else gWs[g]) if live[g] else None
+                 for g in range(G)]
+        return (None,) + tuple(gxs) + tuple(ret_h) + tuple(ret_W)
+
+
+def gate_mix_torch(experts, gate_inputs, gate_weights, members):
+    """The reference's formulation as torch ops: Linear -> softmax -> stack -> matmul per gate."""
+    outs = []
+    for h, W, m in zip(gate_inputs, gate_weights, members):
+        w = torch.nn.functional.linear(h, W).softmax(1)
+        outs.append(torch.matmul(w.unsqueeze(1), torch.stack([experts[e] for e in m], 1)).squeeze(1))
+    return outs
+
+
+def gate_mix_fused(experts, gate_inputs, gate_weights, members):
+    """True when ``gate_mix`` takes csrc/gate_mix.hip for these operands: the switch DCTR_GATE_MIX is not ``0``, everything
+    is a 2-D float32 tensor on the GPU, and the shape lies inside the kernels' envelope (include/dctr.h: at most 32 pool
+    members, 8 gates, 16 members per gate, ``dim`` and every ``H`` at most 1152)."""
+    if os.environ.get("DCTR_GATE_MIX", "1") == "0":
+        return False
+    ts = list(experts) + list(gate_inputs) + list(gate_weights)
+    if not ts or any(t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda for t in ts):
+        return False
+    G = len(members)
+    if G == 0 or any(len(m) == 0 for m in members):
+        return False
+    if G > L.GATE_MAX_GATES or len(experts) > L.GATE_MAX_POOL:      # (the host arrays below hold no more)
+        return False
+    return bool(L.lib().dctr_gate_mix_supported(len(experts), experts[0].shape[1], G, _i32s([len(m) for m in members]),
+                                                _i32s([h.shape[1] for h in gate_inputs])))
+
+
+def gate_mix(experts, gate_inputs, gate_weights, members):
+    """Every gate that draws on one pool of expert outputs -- all gates of an MMOE, one CGC level of a PLE:
+    ``out_g = sum_j softmax(h_g W_g^T)[:, j] * experts[members[g][j]]`` as a list of G ``[B, dim]`` tensors.
+    ``experts``: P tensors ``[B, dim]``; ``gate_inputs[g]``: ``[B, H_g]``; ``gate_weights[g]``: ``[n_g, H_g]`` (bias-free);
+    ``members[g]``: n_g indices into ``experts`` in the order of the reference's ``torch.stack``.  Row-strided views (what
+    ``_hip.mlp.tower(dnn, None, x)`` returns) are read in place.  One launch per direction (csrc/gate_mix.hip) inside
+    the envelope; outside it, or with ``DCTR_GATE_MIX=0``, the same formula as torch ops on the GPU."""
+    experts, gate_inputs, gate_weights = list(experts), list(gate_inputs), list(gate_weights)
+    members = [tuple(int(e) for e in m) for m in members]
+    if not (len(gate_inputs) == len(gate_weights) == len(members)):
+        raise ValueError("gate_mix: one input, one weight and one member list per gate")
+    for m, W, h in zip(members, gate_weights, gate_inputs):
+        if W.shape[0] != len(m) or W.shape[1] != h.shape[1] or any(e < 0 or e >= len(experts) for e in m):
+            raise ValueError("gate_mix: a gate's weight must be [len(members), H] over members inside the pool")
+    L.require_gpu(experts[0], "expert output")
+    if not gate_mix_fused(experts, gate_inputs, gate_weights, members):
+        return gate_mix_torch(experts, gate_inputs, gate_weights, members)
+    ts = experts + gate_inputs + gate_weights
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+    return list(GateMixFunction.apply(_MixMeta(len(experts), members, keep), *ts))

@@ -11,6 +11,7 @@ from .difm import DIFM
 from .din import DIN
 from .fibinet import FiBiNET
 from .ifm import IFM
+from .multitask import ESMM, MMOE, PLE, SharedBottom
 from .nfm import NFM
 from .onn import ONN
 from .pnn import PNN
@@ -18,4 +19,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN", "CCPM", "DIN"]
+           "IFM", "DIFM", "ONN", "CCPM", "DIN", "SharedBottom", "ESMM", "MMOE", "PLE"]

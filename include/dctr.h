@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 30
+#define DCTR_ABI_VERSION 31
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -461,6 +461,52 @@ int dctr_din_attn_bwd(const float* Q, int64_t ld_q, const float* K, int64_t ld_k
                       const int32_t* len, const uint8_t* mask, int32_t n_layers, const int32_t* hidden, int32_t act,
                       int32_t softmax, const float* params, const float* weights, const float* g_out, int64_t ld_gout,
                       float* gQ, int64_t ld_gq, float* gK, int64_t ld_gk, float* g_params, float* workspace,
+                      dctr_stream_t stream);
+
+/* ---- Gate mix of the multi-task models (MMOE's gates, one CGC level of PLE; csrc/gate_mix.hip) ---------------------------
+ * One launch per direction for ALL G gates that draw on one pool of P expert outputs x_e [B, dim] (rows at
+ * x[e] + b*ld_x[e]).  Gate g reads h_g [B, H_g] (rows at h + b*ld_h), the bias-free weight W_g [n_g, H_g] (rows at
+ * W + j*ld_w) and n_g indices member[0..n_g) into the pool (repeats allowed), in the order of the mix:
+ *   z[j] = h_g[b] . W_g[j]        w = softmax(z) (maximum subtracted first)        out_g[b, :] = sum_j w[j] x_{member[j]}[b, :]
+ * The forward writes out_g [B, dim] (rows at out + b*ld_out) and, when w is not NULL, the weights w_g [B, n_g] (contiguous).
+ * Nothing of size [B, n, dim] exists; an expert row is read once per sample for all the gates that use it.
+ * The backward needs w of the forward and takes g_out_g [B, dim] (rows at g_out + b*ld_gout) per gate.  It writes
+ *   g_x[e][b, :] = sum over the gates that use e, in gate order, of (sum_{j: member[j] == e} w_g[b, j]) * g_out_g[b, :]
+ *                  -- every element of every pool member, one writer each, no atomics (zeros for an unused member);
+ *   g_h_g[b, :]  = sum_j dz[j] W_g[j, :],   dz[j] = w[j] * (s[j] - sum_k w[k] s[k]),   s[j] = g_out_g[b] . x_{member[j]}[b]
+ *                  (rows at g_h + b*ld_gh; two gates that read one h get one buffer each);
+ *   gW_g[j, :]   = sum_b dz[j] h_g[b, :]   as [n_g, ld_w]: columns H_g .. ld_w are written as 0.  Every workgroup keeps its
+ *                  partial sums in registers, writes them to the workspace once, and a second kernel adds them in workgroup
+ *                  order: identical bits from run to run.
+ * A gate whose g_out is NULL (nothing downstream used its output) adds nothing to any g_x; its g_h and gW are zeros.
+ * n_g == 1 is legal: the weight is 1, dz is 0.
+ * workspace: dctr_gate_mix_bwd_workspace_floats(B, G, n, ld_w) floats (n, ld_w: HOST arrays of G entries).
+ * DCTR_ENOSUP (dctr_gate_mix_supported == 0) unless 1 <= P <= 32, 1 <= G <= 8, 1 <= n_g <= 16, dim <= 1152, H_g <= 1152
+ * -- every combination inside these bounds runs; there is no LDS condition (the backward stages 16 KB, the forward none).
+ * B == 0 returns DCTR_OK before any buffer check and touches nothing.                                                     */
+#define DCTR_GATE_MAX_GATES 8
+#define DCTR_GATE_MAX_MEMBERS 16
+#define DCTR_GATE_MAX_POOL 32
+#define DCTR_GATE_MAX_WIDTH 1152
+typedef struct {
+  const float* h;      /* [B, H] gate input                                  */
+  const float* W;      /* [n, H] rows at W + j*ld_w                          */
+  float* out;          /* fwd: [B, dim]                                      */
+  float* w;            /* fwd: [B, n] contiguous or NULL; bwd: read          */
+  const float* g_out;  /* bwd: [B, dim] or NULL                              */
+  float* g_h;          /* bwd: [B, H]                                        */
+  float* gW;           /* bwd: [n, ld_w]                                     */
+  int64_t ld_h, ld_w, ld_out, ld_gout, ld_gh;
+  int32_t H, n;
+  int32_t member[DCTR_GATE_MAX_MEMBERS];
+} dctr_gate_t;
+size_t dctr_sizeof_gate(void);
+int dctr_gate_mix_supported(int32_t P, int32_t dim, int32_t G, const int32_t* n, const int32_t* H);
+size_t dctr_gate_mix_bwd_workspace_floats(int32_t B, int32_t G, const int32_t* n, const int32_t* ld_w);
+int dctr_gate_mix_fwd(const float* const* x, const int64_t* ld_x, int32_t P, int32_t dim, int32_t B,
+                      const dctr_gate_t* gates, int32_t G, dctr_stream_t stream);
+int dctr_gate_mix_bwd(const float* const* x, const int64_t* ld_x, int32_t P, int32_t dim, int32_t B,
+                      const dctr_gate_t* gates, int32_t G, float* const* g_x, const int64_t* ld_gx, float* workspace,
                       dctr_stream_t stream);
 
 /* ---- InteractingLayer of AutoInt (interaction.py:328-394): multi-head self-attention over the fields (csrc/interact.hip)
