@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -267,6 +267,11 @@ SIGNATURES = {
                                          _P, _P, _I64, _P, _P]),
     "dctr_din_attn_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32,
                                          _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "dctr_gru_seq_supported": (ctypes.c_int, [_I32, _I32, _P, _I32]),
+    "dctr_gru_seq_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32]),
+    "dctr_gru_seq_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I64, _P, _I64, _P, _P]),
+    "dctr_gru_seq_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _I64, _P, _P, _I64, _P,
+                                        _I64, _P, _I64, _P, _P, _P, _P]),
     "dctr_sizeof_gate": (ctypes.c_size_t, []),
     "dctr_gate_mix_supported": (ctypes.c_int, [_I32, _I32, _I32, _P, _P]),
     "dctr_gate_mix_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32, _P, _P]),

@@ -703,6 +703,69 @@ class DINAttentionFunction(torch.autograd.Function):
         return gQ, (None if shared else gK), gP, None, None, None, None, None, None, None, None
 
 
+GRU_MODE = {"GRU": 0, "AIGRU": 1, "AGRU": 2, "AUGRU": 3}                      # include/dctr.h, dctr_gru_seq_fwd
+
+
+def gru_seq_supported(T, dims, mode="GRU"):
+    """True when csrc/gru_seq.hip runs this shape: H = sum(dims) <= 64, at most 4 segments, 1 <= T <= 128."""
+    if mode not in GRU_MODE or not dims:
+        return False
+    return bool(L.lib().dctr_gru_seq_supported(int(T), len(dims), _i32s(dims), GRU_MODE[mode]))
+
+
+class GRUSeqFunction(torch.autograd.Function):
+    """The variable-length recurrences of DIEN (csrc/gru_seq.hip): ``(X [B, ld_x], att [B, T] | None, params, segs, T,
+    mode, lengths [B] int32, want_states, want_last, keep) -> (states [B, T, H] | None, last [B, H] | None)``.
+
+    ``segs``: one ``(dim, x_off, x_step)`` per segment of the input inside a row of X (the gathered row read in place, or
+    ``[(H, 0, H)]`` for a contiguous ``[B, T*H]``).  ``params``: the packed ``W_ih | W_hh | b_ih | b_hh``.  ``keep``: a
+    backward will follow, so the forward also writes the states (whether asked for or not) and the ``[B, T, 4, H]`` gates."""
+
+    @staticmethod
+    def forward(ctx, X, att, params, segs, T, mode, lengths, want_states, want_last, keep):
+        lib = L.lib()
+        X, ldx = _rows2(X, "GRU input")
+        B, dev = X.shape[0], X.device
+        P = params.detach().float().contiguous()
+        dims, xo, xs = zip(*segs)
+        H, T = int(sum(dims)), int(T)
+        A = att.detach().float().contiguous() if att is not None else None
+        states = torch.empty((B, T, H), dtype=torch.float32, device=dev) if (want_states or keep) else None
+        last = torch.empty((B, H), dtype=torch.float32, device=dev) if want_last else None
+        gates = torch.empty((B, T, 4, H), dtype=torch.float32, device=dev) if keep else None
+        L.check(lib.dctr_gru_seq_fwd(_ptr(X), ldx, B, T, len(dims), _i32s(dims), _i64s(xo), _i64s(xs), _ptr(lengths),
+                                     _ptr(A), GRU_MODE[mode], _ptr(P), _ptr(states), T * H, _ptr(last), H, _ptr(gates),
+                                     L.stream_handle(dev)), "dctr_gru_seq_fwd")
+        if keep:
+            ctx.save_for_backward(X, A, P, lengths, states, gates)
+            ctx.cfg = (tuple(segs), T, mode, bool(want_states), bool(want_last))
+        return (states if want_states else None), last
+
+    @staticmethod
+    def backward(ctx, g_states, g_last):
+        lib = L.lib()
+        X, A, P, lengths, states, gates = ctx.saved_tensors
+        segs, T, mode, want_states, want_last = ctx.cfg
+        B, dev = X.shape[0], X.device
+        ldx = X.stride(0) if B > 1 else X.shape[1]
+        dims, xo, xs = zip(*segs)
+        H = int(sum(dims))
+        gs = g_states.float().contiguous() if (want_states and g_states is not None) else None
+        gl = g_last.float().contiguous() if (want_last and g_last is not None) else None
+        if gs is None and gl is None:
+            gl = torch.zeros((B, H), dtype=torch.float32, device=dev)
+        # (zeros: the kernel writes the segments, whatever else the rows hold gets no gradient from here)
+        gX = torch.zeros(X.shape, dtype=torch.float32, device=dev)
+        gA = torch.empty((B, T), dtype=torch.float32, device=dev) if A is not None else None
+        gP = torch.empty_like(P)
+        ws = torch.empty((max(1, lib.dctr_gru_seq_bwd_workspace_floats(B, H)),), dtype=torch.float32, device=dev)
+        L.check(lib.dctr_gru_seq_bwd(_ptr(X), ldx, B, T, len(dims), _i32s(dims), _i64s(xo), _i64s(xs), _ptr(lengths),
+                                     _ptr(A), GRU_MODE[mode], _ptr(P), _ptr(states), T * H, _ptr(gates), _ptr(gs), T * H,
+                                     _ptr(gl), H, _ptr(gX), gX.shape[1], _ptr(gA), _ptr(gP), _ptr(ws),
+                                     L.stream_handle(dev)), "dctr_gru_seq_bwd")
+        return gX, gA, gP, None, None, None, None, None, None, None
+
+
 class BiPoolFunction(torch.autograd.Function):
     """BiInteractionPooling on the gather's rows (csrc/fm.hip): ``G [B, ld]`` (fields first, dense block at
     ``dense_off``) -> ``[B, r4(D + n_dense)]`` = ``[bi | dense]``, the NFM tower's input; the backward hands back a

@@ -4,5 +4,6 @@ modules."""
 from .activation import Dice, Identity, activation_layer
 from .core import DNN, Conv2dSame, LocalActivationUnit, PredictionLayer
 from .interaction import *  # noqa: F401,F403
-from .sequence import AttentionSequencePoolingLayer, KMaxPooling, SequencePoolingLayer
+from .sequence import (AGRUCell, AttentionSequencePoolingLayer, AUGRUCell, DynamicGRU, KMaxPooling,
+                       SequencePoolingLayer)
 from .utils import concat_fun, slice_arrays

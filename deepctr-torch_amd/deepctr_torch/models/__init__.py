@@ -7,6 +7,7 @@ from .ccpm import CCPM
 from .dcn import DCN
 from .dcnmix import DCNMix
 from .deepfm import DeepFM
+from .dien import DIEN
 from .difm import DIFM
 from .din import DIN
 from .fibinet import FiBiNET
@@ -19,4 +20,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN", "CCPM", "DIN", "SharedBottom", "ESMM", "MMOE", "PLE"]
+           "IFM", "DIFM", "ONN", "CCPM", "DIN", "DIEN", "SharedBottom", "ESMM", "MMOE", "PLE"]

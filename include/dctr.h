@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 31
+#define DCTR_ABI_VERSION 32
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -462,6 +462,50 @@ int dctr_din_attn_bwd(const float* Q, int64_t ld_q, const float* K, int64_t ld_k
                       int32_t softmax, const float* params, const float* weights, const float* g_out, int64_t ld_gout,
                       float* gQ, int64_t ld_gq, float* gK, int64_t ld_gk, float* g_params, float* workspace,
                       dctr_stream_t stream);
+
+/* ---- Variable-length GRU / AIGRU / AGRU / AUGRU of DIEN (dien.py:181-381, sequence.py's AGRUCell / AUGRUCell / DynamicGRU,
+ * torch.nn.GRU on packed sequences; csrc/gru_seq.hip) -------------------------------------------------------------------
+ * Per sample b, with n = clamp(len[b], 0, T), h_0 = 0 and, for t < n, x_t = X(b, t) (mode 1: x_t = a_t * X(b, t)):
+ *   r = sigmoid(W_ir x_t + b_ir + W_hr h + b_hr)      z = sigmoid(W_iz x_t + b_iz + W_hz h + b_hz)
+ *   c = tanh(W_in x_t + b_in + r * (W_hn h + b_hn))
+ *   mode 0 GRU, 1 AIGRU:  h' = (1 - z) * c + z * h                          (torch.nn.GRU's convention)
+ *   mode 2 AGRU:          h' = (1 - a_t) * h + a_t * c                      (z unused: its rows of g_params are exactly 0)
+ *   mode 3 AUGRU:         u = a_t * z;  h' = (1 - u) * h + u * c            (the opposite convention from nn.GRU)
+ * One launch per direction (the backward is followed by a fixed-order reduction); no length ever travels to the host.
+ * len [B] int32 on the device: above T counts as T, 0 or less means no step (dctr_din_attn_fwd's conventions).
+ * Addressing as for the attention's keys, n_seg <= 4 segments of dim[j] floats, H = sum_j dim[j] (input size == hidden
+ * size; dim, x_off, x_step: HOST arrays):   x(b, t, j) = X + b*ld_x + x_off[j] + t*x_step[j]
+ *   (the gathered row read in place: x_step[j] = dim[j]; one contiguous [B, T, H]: n_seg = 1, x_step = H, ld_x = T*H).
+ * The segments' elements must be pairwise distinct addresses (segments may interleave, not overlap): this is the caller's
+ * to guarantee and is not checked; the backward writes every element of gX once, and an overlap would be two writers.
+ * params, one device vector of 6 H^2 + 6 H floats (g_params likewise): W_ih [3H, H] | W_hh [3H, H] | b_ih [3H] | b_hh [3H],
+ * gate order r, z, n as in torch.  att [B, T] contiguous: required in modes 1 to 3, ignored (NULL) in mode 0.
+ * Forward outputs, either of which may be NULL (not both): states(b, t, :) = states + b*ld_states + t*H, h_{t+1} for
+ * t < n and exact zeros for t >= n (pad_packed_sequence's padding), ld_states >= T*H;  last + b*ld_last [H] = h_n (zero
+ * for n = 0).  gates [B, T, 4, H] contiguous or NULL: r, z, c and W_hn h + b_hn of every evaluated step, 16 T H bytes per
+ * sample -- what a backward needs beside `states` (both must then be non-NULL in the forward); positions t >= n are not
+ * written and never read.
+ * The backward takes g_states (same layout, row stride ld_gstates; values at t >= n are ignored) and / or g_last, and
+ * recomputes nothing.  It writes gX with X's addressing (row stride ld_gx): every element of every segment, zeros at
+ * t >= n, nothing outside the segments; g_att [B, T] in modes 1 to 3 (zeros at t >= n; NULL allowed in mode 0); g_params:
+ * every thread owns elements of W_ih / W_hh and adds step after step, sample after sample, the workgroups' rows are added
+ * in order -- no atomics, identical bits from run to run.  workspace: dctr_gru_seq_bwd_workspace_floats(B, H) floats.
+ * DCTR_ENOSUP (dctr_gru_seq_supported == 0) unless H <= 64, 1 <= T <= 128, n_seg <= 4.  The bound on T a MODEL meets first
+ * is DCTR_MAX_UNIT_SLOTS: history (and, under negative sampling, negative history) positions share the candidate's table,
+ * one update slot each plus the candidate's own, so T <= 127 without and 2 T + 1 <= 128, T <= 63, with negative sampling.
+ * H need not be a multiple of 4.  A missing att in modes 1 to 3 is DCTR_EINVAL.  B == 0 returns DCTR_OK before any buffer
+ * check (the backward then zeroes g_params when the shape is valid).                                                       */
+int dctr_gru_seq_supported(int32_t T, int32_t n_seg, const int32_t* dim, int32_t mode);
+size_t dctr_gru_seq_bwd_workspace_floats(int32_t B, int32_t H);
+int dctr_gru_seq_fwd(const float* X, int64_t ld_x, int32_t B, int32_t T, int32_t n_seg, const int32_t* dim,
+                     const int64_t* x_off, const int64_t* x_step, const int32_t* len, const float* att, int32_t mode,
+                     const float* params, float* states, int64_t ld_states, float* last, int64_t ld_last, float* gates,
+                     dctr_stream_t stream);
+int dctr_gru_seq_bwd(const float* X, int64_t ld_x, int32_t B, int32_t T, int32_t n_seg, const int32_t* dim,
+                     const int64_t* x_off, const int64_t* x_step, const int32_t* len, const float* att, int32_t mode,
+                     const float* params, const float* states, int64_t ld_states, const float* gates,
+                     const float* g_states, int64_t ld_gstates, const float* g_last, int64_t ld_glast, float* gX,
+                     int64_t ld_gx, float* g_att, float* g_params, float* workspace, dctr_stream_t stream);
 
 /* ---- Gate mix of the multi-task models (MMOE's gates, one CGC level of PLE; csrc/gate_mix.hip) ---------------------------
  * One launch per direction for ALL G gates that draw on one pool of P expert outputs x_e [B, dim] (rows at
