@@ -1264,6 +1264,9 @@ extern "C" int dctr_cin_layer_bwd(const float* gA, const float* A, int64_t ld_a,
     return DCTR_EINVAL;
   if (B > 0 && !workspace) return DCTR_EINVAL;
   if (relu && !A) return DCTR_EINVAL;
+  if (ld_a < static_cast<int64_t>(O) * D || ld_h < static_cast<int64_t>(h) * D || ld_x0 < static_cast<int64_t>(M) * D ||
+      ld_gh < static_cast<int64_t>(h) * D || ld_gx < static_cast<int64_t>(M) * D)
+    return DCTR_EINVAL;
   if (M > 32) return DCTR_ENOSUP;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int K = h * M;

@@ -1692,11 +1692,12 @@ __global__ __launch_bounds__(kT) void k_cross_mat_bwd(MlpArgs A) {
         if (b < A.B && n < A.ldgx) stg_f32(A.gx + b * A.ldgx + n, n < W ? gin[r * rs + n] + side[k] : 0.f);
       }
     }
-    // columns [Wp, ldgx) of gx (padding) are written as zeros as well
-    for (int e = tid; e < kTM * 4; e += kT) {
-      const int r = e >> 2, n = Wp + (e & 3);
+    // columns [Wp, ldgx) of gx (padding) are written as zeros as well, however wide the padding is
+    const int xp = static_cast<int>(A.ldgx) - Wp;
+    for (int e = tid; e < kTM * xp; e += kT) {
+      const int r = e / xp, n = Wp + (e - r * xp);
       const int64_t b = b0 + r;
-      if (b < A.B && n < A.ldgx) stg_f32(A.gx + b * A.ldgx + n, 0.f);
+      if (b < A.B) stg_f32(A.gx + b * A.ldgx + n, 0.f);
     }
   }
 }
@@ -2367,6 +2368,15 @@ __global__ __launch_bounds__(kTW, 2) void k_mlp_wgrad(WgradArgs A) {
       *(DCTR_GLOBAL f32x4*)(pw + static_cast<int64_t>(row) * Ld.ldw + col) = q;
     }
   }
+  // row padding past the last 64-column tile (ld_w > round_up(K, 64)): no tile owns it and k_mlp_reduce sums all N * ld_w
+  // floats, so the last tile of the row writes its zeros
+  const int xc = Ld.ldw - (k0 + 64);
+  if (k0 + 64 >= Ld.K && xc > 0) {
+    for (int e = tid; e < 64 * xc; e += kTW) {
+      const int row = m0 + e / xc, col = k0 + 64 + e % xc;
+      if (row < Ld.N) stg_f32(pw + static_cast<int64_t>(row) * Ld.ldw + col, 0.f);
+    }
+  }
   if (want_bias && tid < 64 && m0 + tid < Ld.N)
     stg_f32(part + A.off_b[l] + m0 + tid, ((redb[tid] + redb[64 + tid]) + redb[128 + tid]) + redb[192 + tid]);
   MLP_TRACE(A.trace, 3);
@@ -3014,6 +3024,8 @@ extern "C" int dctr_crossnet_mat_bwd(const dctr_mlp_t* m, const float* x, int64_
   if (rc != DCTR_OK) return rc;
   const int W = m->layer[0].K;
   if (!x || !gY || !workspace || ld_x < W || ld_g < W) return DCTR_EINVAL;
+  // (as the forward: k_mlp_wgrad reads layer 0's input in column pairs and counts on ld_x % 4 == 0)
+  if (ld_x % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return DCTR_EALIGN;
   const int rb = check_bwd(m, x, ld_x, B, gx, ld_gx);
   if (rb != DCTR_OK) return rb;
   if (!dctr_crossnet_mat_supported(W, m->n_layers)) return DCTR_ENOSUP;

@@ -684,7 +684,18 @@ int dctr_dense_opt_reg(float* p, const float* g, float* s1, float* s2, const flo
  *   gW   [O, h*M]   (written)      gbias [O]     (written, nullable)
  * gA and A share the leading dimension ld_a.  The backward needs dctr_cin_bwd_workspace_floats(B, h, M, D, O)
  * floats of scratch: the weight gradient is a [O, h*M] x (B*D) GEMM whose batch reduction is split over
- * workgroups; their partial tiles go to the workspace and are summed in a fixed order (no atomics).     */
+ * workgroups; their partial tiles go to the workspace and are summed in a fixed order (no atomics).
+ * Both calls return DCTR_EINVAL for a leading dimension shorter than its row (ld_h < h*D, ld_x0 < M*D, ld_a < O*D,
+ * ld_gh < h*D, ld_gx < M*D) and DCTR_ENOSUP for M > 32, before anything is launched.
+ * The symmetric layer -- H == X0 as POINTERS, ld_h == ld_x0 and h == M: layer 1 of a CIN -- walks every unordered field
+ * pair a <= b once, with the folded weight Wf[o, a, b] = W[o, a*M + b] + W[o, b*M + a] (a < b), W[o, a*M + a] (a == b).
+ * With t(a, b)[n, d] = sum_o Wf[o, a, b] * gY[n, o, d] (gY = gA under the relu mask) and Hh = (M + 1) / 2:
+ *     a <  Hh:   gH[n, a, d] += t(a, b) X0[n, b, d]      gX0[n, b, d] += t(a, b) X0[n, a, d]
+ *     a >= Hh:   gH[n, b, d] += t(a, b) X0[n, a, d]      gX0[n, a, d] += t(a, b) X0[n, b, d]
+ * (a pair a == b adds the same term to both).  Neither buffer is then a gradient by itself; gH + gX0 (gX0 without what
+ * accumulate_x0 found there) is d loss / d X0 of the layer, which is what the caller adds up.  gW and gbias are as in
+ * the general case.  The same values in two distinct buffers take the general kernels: gH = d loss / d H,
+ * gX0 (+)= d loss / d X0.                                                                                            */
 size_t dctr_cin_workspace_floats(int32_t h, int32_t M, int32_t O);
 size_t dctr_cin_bwd_workspace_floats(int32_t B, int32_t h, int32_t M, int32_t D, int32_t O);
 int dctr_cin_layer_fwd(const float* H, int64_t ld_h, const float* X0, int64_t ld_x0, const float* W,
@@ -820,7 +831,10 @@ int dctr_crossnet_vec_bwd(const float* X, int64_t ld_x, int32_t B, int32_t W, in
  * the two calls (the forward parks u_l = x_l W_l^T + b_l there, the backward turns it into d loss / d u_l);  w_out must
  * be NULL.  A workgroup carries 16 samples through all layers (x_0 and x_l stay in LDS); fp32 MFMA 16x16x4.
  * The backward takes gY = d loss / d x_L [B, ld_g] and writes gx [B, ld_gx] = d loss / d x_0, layer[l].gW [W, ld_w]
- * and layer[l].gbias [W] (split-batch partials summed in a fixed order: no atomics);
+ * and layer[l].gbias [W] (split-batch partials summed in a fixed order: no atomics).  All W * ld_w floats of a gW are
+ * written: its padding columns [W, ld_w) receive 0, as the tower's do, and so do gx's [W, ld_gx); the padding of h is
+ * never written.  x and every leading dimension (ld_x, ld_w, ld_h, ld_gx) follow the tower's alignment rule in both
+ * calls: DCTR_EALIGN otherwise.
  * workspace = dctr_crossnet_mat_bwd_workspace_floats(m, B) floats.  dctr_crossnet_mat_supported: W <= 512 (LDS).   */
 struct dctr_mlp;
 int dctr_crossnet_mat_supported(int32_t W, int32_t n_layers);

@@ -22,6 +22,10 @@ def _v(ptr, n):
     return None if a is None else torch.from_numpy(a)
 
 
+def _addr(ptr):
+    return ptr.value if hasattr(ptr, "value") else ptr
+
+
 def _pairs(F):
     return list(itertools.combinations(range(F), 2))
 
@@ -251,6 +255,24 @@ class OpsMixin(object):
     def dctr_cin_bwd_workspace_floats(self, B, h, M, D, O):
         return 16
 
+    @staticmethod
+    def _cin_sym(x0, w, M):
+        """the symmetric layer as the kernels walk it (include/dctr.h, dctr_cin_layer_bwd): every unordered field pair
+        a <= b once with the folded weight; the pairs with a < (M + 1) / 2 take field a from the ``H`` operand and field b
+        from the ``X0`` operand, the others the other way round -> (y, the two operands): autograd then splits the
+        gradient between gH and gX0 as the header says"""
+        B, D = x0.shape[0], x0.shape[1] // M
+        hs, xs = x0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+        hv, xv = hs.reshape(B, M, D).double(), xs.reshape(B, M, D).double()
+        wm = w.double().reshape(-1, M, M)
+        y = 0
+        for a in range(M):
+            for b in range(a, M):
+                wf = wm[:, a, a] if a == b else wm[:, a, b] + wm[:, b, a]
+                z = hv[:, a] * xv[:, b] if a < (M + 1) // 2 else hv[:, b] * xv[:, a]
+                y = y + wf[None, :, None] * z[:, None, :]
+        return y.float(), hs, xs
+
     def dctr_cin_layer_fwd(self, H, ld_h, X0, ld_x0, W, bias, B, h, M, D, O, relu, A, ld_a, ws, stream):
         self.calls.append("cin_layer_fwd")
         y = self._cin(_t(H, B, h * D, ld_h).reshape(B, h, D), _t(X0, B, M * D, ld_x0).reshape(B, M, D), _t(W, O, h * M),
@@ -262,6 +284,8 @@ class OpsMixin(object):
     def dctr_cin_layer_bwd(self, gA, A, ld_a, relu, H, ld_h, X0, ld_x0, W, B, h, M, D, O, gH, ld_gh, gX0, ld_gx,
                            accumulate_x0, gW, gbias, ws, stream):
         self.calls.append("cin_layer_bwd")
+        if ld_a < O * D or ld_h < h * D or ld_x0 < M * D or ld_gh < h * D or ld_gx < M * D:
+            return -1          # DCTR_EINVAL, as the forward
         hh = _t(H, B, h * D, ld_h).clone().requires_grad_(True)
         x0 = _t(X0, B, M * D, ld_x0).clone().requires_grad_(True)
         w = _t(W, O, h * M).clone().requires_grad_(True)
@@ -271,6 +295,10 @@ class OpsMixin(object):
             g = g * (_t(A, B, O * D, ld_a) > 0)
         y = self._cin(hh.reshape(B, h, D), x0.reshape(B, M, D), w, bias, 0)
         gh, gx, gw, gb = _grads(y.reshape(B, -1), [hh, x0, w, bias], g)
+        if _addr(H) == _addr(X0) and ld_h == ld_x0 and h == M:          # the symmetric layer: the documented split
+            ys, hs, xs = self._cin_sym(x0.detach(), w.detach(), M)
+            gh, gx = _grads(ys.reshape(B, -1), [hs, xs], g)
+        _v(ws, 16).zero_()
         _t(gH, B, h * D, ld_gh).copy_(gh)
         dst = _t(gX0, B, M * D, ld_gx)
         dst.copy_(dst + gx if accumulate_x0 else gx)
@@ -377,6 +405,7 @@ class OpsMixin(object):
         for Wl, bl in zip(Ws, bs):
             xl = x0 * (xl @ Wl.t() + bl) + xl
         gs = _grads(xl, [x0] + Ws + bs, _t(gY, B, W, ld_g).double())
+        _t(gx, B, int(ld_gx), ld_gx).zero_()          # (include/dctr.h: the padding columns of gx receive 0)
         _t(gx, B, W, ld_gx).copy_(gs[0])
         for l, e in enumerate(layers):
             full = _t(e.gW, W, e.ld_w, e.ld_w)

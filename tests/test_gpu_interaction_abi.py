@@ -1,4 +1,6 @@
-"""GPU: the older interaction kernels through the C ABI at the sizes where their launchers switch over (csrc/fm.hip,
+"""GPU: the older interaction kernels, and the matrix CrossNet of csrc/mlp.hip (``test_crossnet_mat*``: the rules of the second
+part of interaction_abi's docstring, what each case reaches in the tests' docstrings), through the C ABI at the sizes where
+their launchers switch over (csrc/fm.hip,
 afm.hip, interact.hip, cross.hip and the SENET / inner-product part of pairwise.hip), against float64 on the CPU.
 tests/interaction_abi.py is the driver: padded leading dimensions, sentinel-filled outputs and workspace, the bounds of
 tests/test_gpu_pairwise.py (values 1e-5, gradients 2e-5, CrossNet g_kernels 5e-5, each x max(1, max|ref|)), nothing written
@@ -44,7 +46,9 @@ MI355X, over all cases of this file:
   afm           y 1.2e-7   gE 3.3e-7  gW 2.1e-6  gbias 1.0e-6                   gW1 1.4e-7  gW2 8.2e-8
                 gh 7.6e-6  gp 4.1e-7                          crossnet_vec  Y 1.8e-7  gX 1.5e-7  g_kernels 2.3e-7
   interacting   out 1.4e-6 gE 2.4e-6  gW_Query 1.4e-6  gW_key 2.2e-6            g_bias 4.1e-7
-                gW_Value 1.0e-6  gW_Res 3.1e-7"""
+                gW_Value 1.0e-6  gW_Res 3.1e-7
+and, over max|ref| (not max(1, max|ref|)), for the matrix CrossNet over all its cases:
+  crossnet_mat  Y 2.9e-7   gx 5.4e-7   gW (worst layer) 3.3e-7   gbias (worst layer) 1.6e-7"""
 import ctypes
 
 import numpy as np
@@ -212,6 +216,56 @@ def test_bilinear_envelope():
     torch.cuda.synchronize()
     for t in (out, gE, gW, ws):
         assert float(t.min()) == SENT and float(t.max()) == SENT
+
+
+# ---- CrossNet, matrix parameterisation (csrc/mlp.hip: k_cross_mat_fwd / _bwd + the tower's weight-gradient kernels) --------
+@pytest.mark.parametrize("B,W,L", IA.CROSSNET_MAT_CASES)
+def test_crossnet_mat(B, W, L):
+    """the rules of interaction_abi's second part (max|ref| as the scale, guarded 777 / NaN workspace, gW's padding columns
+    zero).  A workgroup carries 16 samples: B = 1, 15, 16, 17, 33.  W = 1 .. 512 at L = 1: one to eight 64-column tiles of the
+    weight gradient; LDS 16 x 4 x (round_up(W, 64) + 8) x 4 B in the backward -- 51 200 B at W = 192, 67 584 B at W = 193:
+    hipFuncSetAttribute from there -- and 16 x 3 x (round_up(W, 16) + 8) x 4 B in the forward -- 62 976 B at W = 320, 66 048 B
+    at W = 321: the opt-in, 99 840 B at W = 512.  L = 12 is DCTR_MLP_MAX_LAYERS.  At W = 40 the
+    weight gradient's batch slices S = min(B / 64, 16) change at B = 64, 128 and 1024.
+    (Found here: at W = 64, 192, 320, 512 with ld_w = W + 4 the padding columns of gW lie past the last 64-column tile of
+    k_mlp_wgrad; no partial was written there and k_mlp_reduce summed what the workspace held -- NaN under this driver.
+    The last tile of a row writes those zeros now.)"""
+    IA.CrossNetMatCase(_lib(), DEV, B, W, L).check()
+
+
+def test_crossnet_mat_smallest_shapes():
+    for D in IA.SMALL_D:
+        for case in IA.smallest(_lib(), DEV, "crossnet_mat", D):
+            case.check()
+
+
+def _mat_refused(case, code, forward=True):
+    if forward:
+        assert case.forward() == code
+        assert case.sentinel_everywhere(case.fwd_out)
+    assert case.backward() == code
+    assert case.sentinel_everywhere(case.bwd_out)
+
+
+def test_crossnet_mat_envelope_and_argument_checks():
+    """W = 513: DCTR_ENOSUP; a leading dimension that is no multiple of 4: DCTR_EALIGN; a non-NULL w_out: DCTR_EINVAL -- each
+    before any launch, the outputs untouched; B = 0: DCTR_OK, nothing written"""
+    lib = _lib()
+    assert lib.dctr_crossnet_mat_supported(512, 1) == 1 and lib.dctr_crossnet_mat_supported(513, 1) == 0
+    _mat_refused(IA.CrossNetMatCase(lib, DEV, 2, 513, 1), ENOSUP)
+    for which in ("x", "w", "h"):          # W = 5 in rows of 8 floats, told 7
+        case = IA.CrossNetMatCase(lib, DEV, 2, 5, 2)
+        case.force_ld[which] = 7
+        _mat_refused(case, IA.EALIGN)
+    case = IA.CrossNetMatCase(lib, DEV, 2, 5, 2)
+    case.force_ld["gx"] = 7
+    _mat_refused(case, IA.EALIGN, forward=False)
+    case = IA.CrossNetMatCase(lib, DEV, 2, 5, 2)
+    case.w_out = case.bs[0]
+    _mat_refused(case, IA.EINVAL)
+    case = IA.CrossNetMatCase(lib, DEV, 1, 5, 2)
+    case.nB = 0
+    _mat_refused(case, 0)
 
 
 def test_zz_report():
