@@ -25,13 +25,6 @@ namespace {
 constexpr int kT = 256;       // threads per workgroup
 constexpr int kCols = 256;    // columns per workgroup
 
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// row of accumulator register r held by a lane of half p (32x32 C/D layout)
-__device__ __forceinline__ int acc_row(int r, int p) { return (r & 3) + 8 * (r >> 2) + 4 * p; }
-
 // W [O, h*M] (conv1ds.k.weight squeezed) -> Wt [h][M_pad][O_pad], zero padded
 // sym (layer 1: H IS X0, so Z[(h, m)] = Z[(m, h)]): the two weights of a field pair are folded onto its m > h entry,
 //     Wt[h][m] = W[h][m] + W[m][h] (m > h),  W[h][h] (m == h),  0 (m < h)
@@ -190,9 +183,9 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_fwd(const float* __restr
   for (int ot = 0; ot < OT; ++ot) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int o = o_base + ot * 32 + acc_row(r, p);
+      const int o = o_base + ot * 32 + acc_row32(r, p);
       if (o < O) {
-        const float bo = x0s[ot * 32 + acc_row(r, p)];
+        const float bo = x0s[ot * 32 + acc_row32(r, p)];
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
           if (cv[t]) {
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_bwd_data(const float* __
   for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mm = acc_row(r, p);
+      const int mm = acc_row32(r, p);
       const float v = ldg_f32(X0 + bb[t] * ldx0 + (mm < M ? mm : M - 1) * D + dd[t]);
       x0r[t][r] = (cv[t] && mm < M) ? v : 0.f;
       gxa[t][r] = 0.f;
@@ -353,7 +346,7 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_bwd_data(const float* __
   for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mm = acc_row(r, p);
+      const int mm = acc_row32(r, p);
       if (cv[t] && mm < M) {
         float* dst = gX0 + bb[t] * ldgx + mm * D + dd[t];
         stg_f32(dst, acc_x ? ldg_f32(dst) + gxa[t][r] : gxa[t][r]);
@@ -653,7 +646,7 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_bwd_data_sym(const float
   for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mm = acc_row(r, p);
+      const int mm = acc_row32(r, p);
       const float v = ldg_f32(X0 + bb[t] * ldx0 + (mm < M ? mm : M - 1) * D + dd[t]);
       x0r[t][r] = (cv[t] && mm < M) ? v : 0.f;
       gxa[t][r] = 0.f;
@@ -713,11 +706,11 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_bwd_data_sym(const float
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (r < RU) {
-          const bool main = acc_row(r, p) >= j;
+          const bool main = acc_row32(r, p) >= j;
           const float zm = main ? acc[t][r] : 0.f, zu = main ? 0.f : acc[t][r];
           pm += zm * x0r[t][r];
           gxa[t][r] += zm * hj[t];
-          pu += zu * xu[acc_row(r, p) * kCols + col];
+          pu += zu * xu[acc_row32(r, p) * kCols + col];
           gxu[t][r] += zu * hb;
         } else {            // rows 16..31: always a main pair (zero weights when there is none)
           pm += acc[t][r] * x0r[t][r];
@@ -749,13 +742,13 @@ __global__ __launch_bounds__(kT * 2 / CT, 1) void k_cin_bwd_data_sym(const float
 #pragma unroll
   for (int t = 0; t < CT; ++t)
 #pragma unroll
-    for (int r = 0; r < RU; ++r) up[acc_row(r, p) * kCols + wv * (32 * CT) + t * 32 + jl] = gxu[t][r];
+    for (int r = 0; r < RU; ++r) up[acc_row32(r, p) * kCols + wv * (32 * CT) + t * 32 + jl] = gxu[t][r];
   __syncthreads();
 #pragma unroll
   for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mm = acc_row(r, p);
+      const int mm = acc_row32(r, p);
       if (cv[t] && mm < M) {
         float v = gxa[t][r];
         if (mm >= Hh && mm - Hh < 16) v += up[(mm - Hh) * kCols + wv * (32 * CT) + t * 32 + jl];
@@ -953,7 +946,7 @@ __global__ __launch_bounds__(kT, 2) void k_cin_wgrad(const float* __restrict__ g
         for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int o = ot * 32 + acc_row(r, p);
+            const int o = ot * 32 + acc_row32(r, p);
             if (o < O) stg_f32(dst + static_cast<int64_t>(o) * K + kk[nt], acc[ot][nt][r]);
           }
       }

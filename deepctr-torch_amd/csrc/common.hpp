@@ -22,6 +22,16 @@ struct Strip {
   float v[VEC];
 };
 
+// v_mfma_f32_16x16x4_f32 / v_mfma_f32_32x32x2_f32 (exact fp32)
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+// row of accumulator register r held by a lane of half p (32x32 C/D layout)
+__device__ __forceinline__ int acc_row32(int r, int p) { return (r & 3) + 8 * (r >> 2) + 4 * p; }
+
 template <int VEC>
 __device__ __forceinline__ Strip<VEC> strip_zero() {
   Strip<VEC> r;

@@ -24,66 +24,16 @@
 // 64x64 output tile (2x2 MFMA 32x32x2) over a slice of the batch; the four waves of a workgroup take four batch
 // slices of the same tile and are summed through LDS in wave order; S workgroups per tile write S partial slabs
 // that k_mlp_reduce adds in slab order: bit-reproducible, which keeps data-parallel replicas identical.
-#include "common.hpp"
-
-using namespace dctr;
+//
+// The general forward / backward-data bodies, which the CrossNet kernels of cross_tower.hip run too, are in tower_tiles.hpp;
+// this file has the fast bodies, the embedding gather stage, the fused train kernels and the weight gradients.
+// (Why the weight gradients are not a unit of their own, and the two tile CrossNets share one: round_up has internal
+// linkage, and in a unit whose device code passes it ONE multiple only -- 8 in k_mlp_wgrad alone, 16 in k_cross_mat_* alone
+// -- the compiler specialises it before it is inlined; those kernels then get other machine code than they have beside
+// callers with other multiples.  tools/isa_diff.py compares the listings.)
+#include "tower_tiles.hpp"
 
 namespace {
-
-constexpr int kTM = 16;        // samples per workgroup (forward / backward-data)
-constexpr int kT = 512;        // threads per workgroup (forward / backward-data)
-constexpr int kWaves = kT / 64;
-constexpr int kKC = 512;       // columns of the tower input staged in LDS at a time
-constexpr int kNTMax = 4;      // output tiles a wave carries at once (forward)
-constexpr int kTW = 256;       // threads per workgroup (wgrad)
-constexpr int kMaxL = DCTR_MLP_MAX_LAYERS;
-// Padding floats behind every LDS tile row (row strides are a multiple of 16 plus this).  The A operand of
-// v_mfma_f32_16x16x4 is read as one ds_read_b128 per lane -- lane (g = lane / 16, c = lane % 16) takes the 16 bytes at
-// row c, column 4 g of the K block -- and that instruction is served in four FIXED 16-lane groups
-// ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...: MI355X_MICROARCH.md, LDS) over 16 slots of 16 bytes.  With a row pitch of
-// s slots the lane's slot is (c s + g) mod 16: for odd s (the +4 padding of rounds 1-3: s = 13 and 1) every group has two
-// lanes on one slot -- SQ_LDS_BANK_CONFLICT was 40 % of the tower's LDS cycles; for s = 2 mod 4 the eight rows of a group
-// that share g land on eight distinct even (g = 0, 2) or odd (g = 1, 3) slots: conflict-free.  s = 2 mod 4 <=> pitch = 8 mod 16.
-constexpr int kPad = 8;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row32(int r, int p) { return (r & 3) + 8 * (r >> 2) + 4 * p; }
-
-__host__ __device__ __forceinline__ int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-struct LayerDev {
-  const float* W;
-  const float* bias;
-  float* h;
-  float* dh;
-  int K, N, ldw, ldh, relu;
-};
-
-struct MlpArgs {
-  LayerDev L[kMaxL];
-  int n_layers;
-  int B;
-  const float* x;
-  int64_t ldx;
-  const float* w_out;
-  float* logit;      // forward: [B] (with w_out)
-  const float* g;    // backward: [B] (with w_out) or [B, ldg]
-  int64_t ldg;
-  float* gx;         // backward: [B, ldgx] nullable
-  int64_t ldgx;
-  int rsx, rsh;      // LDS row strides (floats) of the forward
-  int kc;            // columns of the tower input staged in LDS at a time (<= kKC; smaller for wide towers)
-  int rsd;           // LDS row stride of the backward-data pass
-  int fast;          // 1: the tower fits the fast bodies (mlp_fwd_fast / mlp_bwd_fast)
-  uint32_t wmask;    // diagnostics: AND mask on the weight byte offsets (0xffffffff normally; DCTR_MLP_WMASK in the diag build
-                     // folds the weight stream onto a few KB that stay in L1 -- timing experiment, wrong results)
-  unsigned long long* trace;
-};
 
 // head + loss of the fused train kernel (csrc/head.hip has the stand-alone version)
 struct HeadArgs {
@@ -96,8 +46,6 @@ struct HeadArgs {
   float* part_loss;     // [n workgroups] per-workgroup partial sums
   float* part_gbias;    // [n workgroups]
 };
-
-__device__ __forceinline__ f32x4 ldg_f4(const float* p) { return *(const DCTR_GLOBAL f32x4*)p; }
 
 // The embedding lookup as the fused train kernel's input stage (dctr_embed_tower_train_step; round 4): a workgroup gathers
 // the rows of its own 16 samples straight from the tables while it would otherwise wait for the gather kernel's output --
@@ -132,14 +80,7 @@ struct GatherArgs {
 };
 
 
-// diagnostics (tools/mlp_trace.py): 16 wall_clock64 stamps per workgroup, or NULL -- only in the DCTR_DIAG build
-// (libdctr_hip_diag.so); the shipped library keeps no mutable global state
 #ifdef DCTR_DIAG
-unsigned long long* g_mlp_trace = nullptr;
-#define MLP_TRACE(T, slot)                                                                   \
-  do {                                                                                       \
-    if ((T) && threadIdx.x == 0) (T)[blockIdx.x * 16ull + (slot)] = wall_clock64();          \
-  } while (0)
 // The fast bodies stamp into LDS (every lane of the wave stores the same 32-bit s_memrealtime value to the slot: no
 // branch, no register pressure; the last wave through a point wins, i.e. the slot holds the slowest wave's time) and the
 // kernel writes the slots out at its very end, so a stamp does not split a software-pipelined region.
@@ -169,8 +110,6 @@ unsigned long long* g_mlp_trace = nullptr;
       for (int i_ = 0; i_ < 16; ++i_) (T)[blockIdx.x * 16ull + i_] = ft_[i_];                               \
   } while (0)
 #else
-static unsigned long long* const g_mlp_trace = nullptr;
-#define MLP_TRACE(T, slot) do { } while (0)
 #define FT_DECL do { } while (0)
 #define FT(slot) do { } while (0)
 #define FT_ARG
@@ -180,479 +119,6 @@ static unsigned long long* const g_mlp_trace = nullptr;
 #define FT_FLUSH_B(T) do { } while (0)
 #define FT_FLUSH(T) do { } while (0)
 #endif
-
-// the fast bodies (defined behind the general ones)
-template <bool GATHER>
-__device__ __forceinline__ const float* mlp_fwd_fast(const MlpArgs& A, float* smem, float* logit_lds, const GatherArgs& G,
-                                                     float* p0s, float* p1s FT_ARG);
-__device__ __forceinline__ void mlp_bwd_fast(const MlpArgs& A, float* smem, const float* g_lds, const float* hb0,
-                                             const float* hb1, int rs_h FT_ARG);
-
-// ------------------------------------------------------------------------------------------------------------
-// forward
-// ------------------------------------------------------------------------------------------------------------
-// NT output tiles (16 columns each) of one layer over the K range [kg0, kg0 + klen) whose A rows sit in LDS.
-//  * No load in the loop is predicated (a predicated load becomes a branch and serialises the loop on memory
-//    latency): columns past N re-read row N-1 (their results are dropped by the epilogue) and a dwordx4 that
-//    would leave the row is pulled back inside it (its A elements are zero, and weights are finite).
-//  * The weight stream runs kPD-1 iterations ahead of the matrix pipe in a register ring (one iteration is
-//    4*NT MFMAs = 128*NT cycles, so fewer tiles => deeper ring to cover the L2 latency).
-//  * Addresses are a uniform base + one 32-bit lane offset per tile (+ a per-iteration byte offset shared by the
-//    tiles): ~NT+2 vector ALU instructions per iteration next to 4*NT MFMAs.
-//  * A tile's k-steps alternate between KS accumulators so that at least four independent MFMA chains are in
-//    flight per wave (a dependent 16x16x4 chain leaves the matrix pipe idle between issues).
-//  * `between()` runs after the ring prologue has been issued: the kernel stages the A chunk there, so the
-//    first weight loads overlap the staging's own memory latency.
-template <int NT, typename Between>
-__device__ __forceinline__ void fwd_tiles(const float* As, int rs, int kg0, int klen, const LayerDev& Ld,
-                                          int tile0, f32x4* acc, int g, int c, Between between) {
-  constexpr int kPD = NT == 1 ? 12 : (NT == 2 ? 8 : (NT == 3 ? 6 : 4));
-  constexpr int KS = NT >= 4 ? 1 : (NT >= 2 ? 2 : 4);
-  const DCTR_GLOBAL char* wbase = (const DCTR_GLOBAL char*)Ld.W;
-  // first column this lane reads, pulled back inside the row when the (16-wide, zero-padded in LDS) K range is wider
-  // than the weight row itself (K < 12: the lane's A elements are zero there).  Was computed unsigned: for tiny K the
-  // offset wrapped and the last row's loads left the allocation (round 2, tools/uninit_probe.py).
-  const int col0 = (kg0 + 4 * g) < (Ld.ldw - 4) ? (kg0 + 4 * g) : (Ld.ldw - 4);
-  uint32_t voff[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    int n = (tile0 + t * kWaves) * 16 + c;
-    n = n < Ld.N ? n : Ld.N - 1;
-    voff[t] = (static_cast<uint32_t>(n) * static_cast<uint32_t>(Ld.ldw) + static_cast<uint32_t>(col0)) * 4u;
-  }
-  const float* ap = As + c * rs + 4 * g;
-  const int n_it = klen >> 4;
-  const uint32_t omax = static_cast<uint32_t>(Ld.ldw - 4 - col0) * 4u;  // largest in-row byte offset (>= 0)
-  auto woff = [&](int it) -> uint32_t {
-    it = it < n_it ? it : n_it - 1;                       // scalar: `it` is wave-uniform
-    const uint32_t o = static_cast<uint32_t>(it) << 6;
-    return o < omax ? o : omax;
-  };
-  f32x4 ring[kPD][NT];
-#pragma unroll
-  for (int d = 0; d < kPD - 1; ++d) {
-    const uint32_t o = woff(d);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) ring[d][t] = *(const DCTR_GLOBAL f32x4*)(wbase + (voff[t] + o));
-  }
-  between();
-  f32x4 accs[NT][KS];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    accs[t][0] = acc[t];
-#pragma unroll
-    for (int k = 1; k < KS; ++k) accs[t][k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const int n_grp = n_it / kPD, rem = n_it - n_grp * kPD;
-  f32x4 a_nxt = *reinterpret_cast<const f32x4*>(ap);
-  for (int gi = 0; gi < n_grp; ++gi) {
-#pragma unroll
-    for (int d = 0; d < kPD; ++d) {
-      const int it = gi * kPD + d;
-      const uint32_t o = woff(it + kPD - 1);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) ring[(d + kPD - 1) % kPD][t] = *(const DCTR_GLOBAL f32x4*)(wbase + (voff[t] + o));
-      const f32x4 a4 = a_nxt;
-      const int itn = it + 1 < n_it ? it + 1 : it;
-      a_nxt = *reinterpret_cast<const f32x4*>(ap + (itn << 4));
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) accs[t][j % KS] = mfma16(a4[j], ring[d][t][j], accs[t][j % KS]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < kPD - 1; ++d) {
-    if (d < rem) {
-      const int it = n_grp * kPD + d;
-      const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + (it << 4));
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) accs[t][j % KS] = mfma16(a4[j], ring[d][t][j], accs[t][j % KS]);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    f32x4 r = accs[t][0];
-#pragma unroll
-    for (int k = 1; k < KS; ++k) r += accs[t][k];
-    acc[t] = r;
-  }
-}
-
-template <typename Between>
-__device__ __forceinline__ void fwd_dispatch(int nt, const float* As, int rs, int kg0, int klen, const LayerDev& Ld,
-                                             int tile0, f32x4* acc, int g, int c, Between between) {
-  switch (nt) {
-    case 1: fwd_tiles<1>(As, rs, kg0, klen, Ld, tile0, acc, g, c, between); break;
-    case 2: fwd_tiles<2>(As, rs, kg0, klen, Ld, tile0, acc, g, c, between); break;
-    case 3: fwd_tiles<3>(As, rs, kg0, klen, Ld, tile0, acc, g, c, between); break;
-    case 4: fwd_tiles<4>(As, rs, kg0, klen, Ld, tile0, acc, g, c, between); break;
-    default: between(); break;   // a wave without tiles still takes part in the staging barriers
-  }
-}
-
-// the forward of one 16-sample row tile; `logit_lds` (nullable): [16] LDS floats that receive the projection.
-// CROSS: the layers are the matrix form of CrossNet (interaction.py:448-451) instead of Linear + activation:
-//     u_l = x_l W_l^T + b_l ;  x_{l+1} = x_0 (.) u_l + x_l          (every layer W x W, x_0 = the staged input tile)
-// u_l is parked in the layer's `dh` buffer (the backward needs it and overwrites it with its own d loss / d u_l).
-// Returns the LDS tile [16][rsh] that holds the top layer's output when the body ends.
-template <bool CROSS = false>
-__device__ __forceinline__ const float* mlp_fwd_body(const MlpArgs& A, float* smem, float* logit_lds) {
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int b0 = blockIdx.x * kTM;
-  const int rsx = A.rsx, rsh = A.rsh;
-  float* xs = smem;               // [16][rsx]  chunk of the tower input
-  float* hb0 = xs + kTM * rsx;    // [16][rsh]  ping
-  float* hb1 = hb0 + kTM * rsh;   // [16][rsh]  pong
-  const int K0 = A.L[0].K, K0p = round_up(K0, 16);
-  const int kcw = K0p < A.kc ? K0p : A.kc;
-  MLP_TRACE(A.trace, 0);
-  // the projection's weights, requested now and used after the last layer (it used to wait for them there)
-  float wo_pre[4] = {0.f, 0.f, 0.f, 0.f};
-  if (A.w_out && (A.logit || logit_lds)) {
-    const int ntop = A.L[A.n_layers - 1].N;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wo_pre[i] = ldg_f32(A.w_out + ((lane + 64 * i) < ntop ? (lane + 64 * i) : ntop - 1));
-  }
-
-  const float* in = nullptr;
-  for (int l = 0; l < A.n_layers; ++l) {
-    const LayerDev& Ld = A.L[l];
-    const int ntile = (Ld.N + 15) >> 4;
-    float* outb = (l & 1) ? hb1 : hb0;
-    for (int tbase = 0; tbase < ntile; tbase += kWaves * kNTMax) {
-      const int tile0 = tbase + wv;
-      int nt = 0;
-#pragma unroll
-      for (int t = 0; t < kNTMax; ++t) nt += (tile0 + t * kWaves < ntile) ? 1 : 0;
-      f32x4 acc[kNTMax];
-#pragma unroll
-      for (int t = 0; t < kNTMax; ++t) {
-        const int n = (tile0 + t * kWaves) * 16 + c;
-        const float bv = (t < nt && n < Ld.N && Ld.bias) ? ldg_f32(Ld.bias + n) : 0.f;
-        acc[t] = f32x4{bv, bv, bv, bv};
-      }
-      if (l == 0) {
-        for (int kc = 0; kc < K0p; kc += kcw) {
-          const int klen = (K0p - kc) < kcw ? (K0p - kc) : kcw;
-          auto stage = [&]() {
-            __syncthreads();  // the previous chunk (or pass) is consumed
-            // No load here is predicated (a predicated load is a branch around the load with its own vmcnt(0): the
-            // loop used to be one memory round trip per iteration, 4.9 us for the 27 KB tile of the DeepFM tower --
-            // round 3): rows past B re-read row B-1, a dwordx4 that would leave the row is pulled back inside it
-            // (ld_x % 4 == 0), and what lies past K0 or B is zeroed by a select on the way to LDS.
-            const int q4 = klen >> 2, n_e = kTM * q4;
-            const int64_t blast = A.B - 1;
-            for (int e0 = 0; e0 < n_e; e0 += 4 * kT) {
-              f32x4 v[4];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                int e = e0 + i * kT + tid;
-                e = e < n_e ? e : n_e - 1;
-                const int r = e / q4, q = e - r * q4;
-                const int k = kc + 4 * q;
-                const int64_t b = (b0 + r) < blast ? (b0 + r) : blast;
-                const int64_t kk = k < A.ldx - 4 ? k : A.ldx - 4;
-                v[i] = ldg_f4(A.x + b * A.ldx + kk);
-              }
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                const int e = e0 + i * kT + tid;
-                if (e < n_e) {
-                  const int r = e / q4, q = e - r * q4;
-                  const int k = kc + 4 * q;
-                  const bool rv = b0 + r < A.B && k <= A.ldx - 4;
-                  f32x4 w;
-                  w.x = (rv && k < K0) ? v[i].x : 0.f;
-                  w.y = (rv && k + 1 < K0) ? v[i].y : 0.f;
-                  w.z = (rv && k + 2 < K0) ? v[i].z : 0.f;
-                  w.w = (rv && k + 3 < K0) ? v[i].w : 0.f;
-                  *reinterpret_cast<f32x4*>(xs + r * rsx + 4 * q) = w;
-                }
-              }
-            }
-            __syncthreads();
-            if (kc == 0 && tbase == 0) MLP_TRACE(A.trace, 1);
-          };
-          fwd_dispatch(nt, xs, rsx, kc, klen, Ld, tile0, acc, g, c, stage);
-        }
-      } else {
-        fwd_dispatch(nt, in, rsh, 0, round_up(Ld.K, 16), Ld, tile0, acc, g, c, []() {});
-      }
-      if (tbase == 0) MLP_TRACE(A.trace, 2 + 3 * l);
-      // epilogue: activation; keep the tile in LDS for the next layer, save it for the backward
-#pragma unroll
-      for (int t = 0; t < kNTMax; ++t) {
-        if (t < nt) {
-          const int n = (tile0 + t * kWaves) * 16 + c;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = 4 * g + r;
-            float v = acc[t][r];
-            if (CROSS) {
-              const float x0v = xs[row * rsx + n];                  // (K0 <= kKC: the whole input tile is staged)
-              const float xlv = (l == 0) ? x0v : in[row * rsh + n];
-              if (Ld.dh && n < Ld.N && b0 + row < A.B) stg_f32(Ld.dh + static_cast<int64_t>(b0 + row) * Ld.ldh + n, v);
-              v = x0v * v + xlv;
-            } else if (Ld.relu) {
-              v = v > 0.f ? v : 0.f;
-            }
-            if (n >= Ld.N) v = 0.f;
-            outb[row * rsh + n] = v;
-            if (Ld.h && n < Ld.N && b0 + row < A.B) stg_f32(Ld.h + static_cast<int64_t>(b0 + row) * Ld.ldh + n, v);
-          }
-        }
-      }
-    }
-    MLP_TRACE(A.trace, 3 + 3 * l);
-    __syncthreads();
-    MLP_TRACE(A.trace, 4 + 3 * l);
-    in = outb;
-  }
-  if (A.w_out && (A.logit || logit_lds)) {  // dnn_linear: logit[b] = h_last[b, :] . w_out
-    const LayerDev& Lt = A.L[A.n_layers - 1];
-    for (int row = wv; row < kTM; row += kWaves) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (lane + 64 * i < Lt.N) s += in[row * rsh + lane + 64 * i] * wo_pre[i];
-      for (int n = lane + 256; n < Lt.N; n += 64) s += in[row * rsh + n] * ldg_f32(A.w_out + n);
-      s = wave_sum(s);
-      if (lane == 0) {
-        if (A.logit && b0 + row < A.B) stg_f32(A.logit + b0 + row, s);
-        if (logit_lds) logit_lds[row] = s;
-      }
-    }
-  }
-  MLP_TRACE(A.trace, 15);
-  return in;
-}
-
-__global__ __launch_bounds__(kT) void k_mlp_fwd(MlpArgs A) {
-  extern __shared__ __align__(16) float smem[];
-  FT_DECL;
-#ifdef DCTR_FAST_ONLY   // (ISA reading aid: compile the fast body alone)
-  mlp_fwd_fast<false>(A, smem, nullptr, GatherArgs{}, nullptr, nullptr FT_PASS);
-#else
-  if (A.fast) {
-    mlp_fwd_fast<false>(A, smem, nullptr, GatherArgs{}, nullptr, nullptr FT_PASS);
-    FT_FLUSH(A.trace);
-  } else {
-    mlp_fwd_body<false>(A, smem, nullptr);
-  }
-#endif
-}
-
-__global__ __launch_bounds__(kT) void k_cross_mat_fwd(MlpArgs A) {
-  extern __shared__ __align__(16) float smem[];
-  mlp_fwd_body<true>(A, smem, nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// backward, data path: dH_l (gradient w.r.t. the pre-activation of layer l) for every layer, then d/d input
-// ------------------------------------------------------------------------------------------------------------
-// Q consecutive output columns per lane (a group of 16 Q columns per wave pass) of d loss / d input of layer l:
-//     out[16 rows][16 Q cols] = din[16][Np] . W_l[Np][cols]          (reduction over the layer's N outputs)
-// then the epilogue: relu mask of the layer below, into LDS (`dout`) for the next pass and into its `dh`; at l = 0 into gx.
-//  * Q = 4: 64-column groups, dwordx4 weight loads; Q = 2: 32-column groups, dwordx2 -- chosen when the 64-column groups
-//    would leave waves without work (a 256-wide layer has 4 of them for 8 waves: round 3).
-//  * ldw % 4 == 0: a load at col0 < ldw stays inside the row.  Columns past it re-read column 0 and rows past N re-read
-//    row N-1 (the A operand is zero there): no predicated loads in the loop.
-//  * The relu mask of the layer below (its saved output h) is requested BEFORE the weight ring and the MFMA loop and
-//    consumed in the epilogue (it used to be loaded there: one exposed round trip per pass).
-template <int Q>
-__device__ __forceinline__ void bwd_cols(const MlpArgs& A, int l, const float* din, float* dout, int rs, int gb, int b0,
-                                         int g, int c) {
-  typedef float vecq __attribute__((ext_vector_type(Q)));
-  const LayerDev& Ld = A.L[l];
-  const int Np = round_up(Ld.N, 16);      // reduction length
-  const int Kp = round_up(Ld.K, 16);      // output columns kept in LDS for the next (lower) layer
-  const int col0 = 16 * Q * gb + Q * c;
-  const int colc = col0 < Ld.ldw ? col0 : 0;
-  const int lp = l > 0 ? l - 1 : 0;
-  const LayerDev& Lp = A.L[lp];           // (l == 0: only its buffer is borrowed as a valid address)
-  vecq hpre[4];
-  {
-    const int cc = col0 < Lp.ldh - Q ? col0 : Lp.ldh - Q;
-    const int64_t blast = A.B - 1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t b = (b0 + 4 * g + r) < blast ? (b0 + 4 * g + r) : blast;
-      hpre[r] = *(const DCTR_GLOBAL vecq*)(Lp.h + b * Lp.ldh + cc);
-    }
-  }
-  f32x4 acc[Q];
-#pragma unroll
-  for (int q = 0; q < Q; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float* ap = din + c * rs + 4 * g;
-  const int n_it = Np >> 4;
-  // uniform base + 32-bit lane offsets: row n = 16 it + 4 g + j of W starts at byte (n * ldw + colc) * 4
-  const DCTR_GLOBAL char* wbase = (const DCTR_GLOBAL char*)Ld.W;
-  const uint32_t ldw4 = static_cast<uint32_t>(Ld.ldw) * 4u;
-  const uint32_t vlast = static_cast<uint32_t>(Ld.N - 1) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-  uint32_t vrow[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) vrow[j] = static_cast<uint32_t>(4 * g + j) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-  auto wld = [&](int it, vecq* dst) {
-    it = it < n_it ? it : n_it - 1;                               // scalar
-    const uint32_t so = static_cast<uint32_t>(it) * 16u * ldw4;  // scalar
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t o = vrow[j] + so;
-      o = o < vlast ? o : vlast;                                  // rows past N re-read row N-1 (A is 0 there)
-      dst[j] = *(const DCTR_GLOBAL vecq*)(wbase + o);
-    }
-  };
-  constexpr int PD = Q == 4 ? 5 : 8;      // an iteration is 4 Q MFMAs: fewer columns => deeper ring to cover the L2 latency
-  vecq ring[PD][4];
-#pragma unroll
-  for (int d = 0; d < PD - 1; ++d) wld(d, ring[d]);
-  const int n_grp = n_it / PD, rem = n_it - n_grp * PD;
-  f32x4 a_nxt = *reinterpret_cast<const f32x4*>(ap);
-  for (int gi = 0; gi < n_grp; ++gi) {
-#pragma unroll
-    for (int d = 0; d < PD; ++d) {
-      const int it = gi * PD + d;
-      wld(it + PD - 1, ring[(d + PD - 1) % PD]);
-      const f32x4 a4 = a_nxt;
-      const int itn = it + 1 < n_it ? it + 1 : it;
-      a_nxt = *reinterpret_cast<const f32x4*>(ap + (itn << 4));
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < PD - 1; ++d) {
-    if (d < rem) {
-      const int it = n_grp * PD + d;
-      const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + (it << 4));
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 4 * g + r;
-    const int64_t b = b0 + row;
-    vecq v;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = acc[q][r];
-    if (l > 0) {
-      if (col0 < Kp) {    // Lp.N == Ld.K
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          float o = v[q];
-          if (Lp.relu && !(hpre[r][q] > 0.f)) o = 0.f;
-          if (col0 + q >= Lp.N || b >= A.B) o = 0.f;
-          v[q] = o;
-        }
-        *reinterpret_cast<vecq*>(dout + row * rs + col0) = v;
-        if (Lp.dh && b < A.B) {
-          if (col0 + Q - 1 < Lp.N) *(DCTR_GLOBAL vecq*)(Lp.dh + b * Lp.ldh + col0) = v;
-          else
-            for (int q = 0; q < Q; ++q)
-              if (col0 + q < Lp.N) stg_f32(Lp.dh + b * Lp.ldh + col0 + q, v[q]);
-        }
-      }
-    } else if (b < A.B) {
-      // columns [K, ldgx) of gx are padding: written as zeros so that no garbage is ever handed on
-      if (col0 + Q - 1 < A.ldgx) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q)
-          if (col0 + q >= Ld.K) v[q] = 0.f;
-        *(DCTR_GLOBAL vecq*)(A.gx + b * A.ldgx + col0) = v;
-      } else {
-        for (int q = 0; q < Q; ++q)
-          if (col0 + q < A.ldgx) stg_f32(A.gx + b * A.ldgx + col0 + q, col0 + q < Ld.K ? v[q] : 0.f);
-      }
-    }
-  }
-}
-
-// the backward-data pass of one row tile; `g_lds` (nullable): [16] LDS floats holding d loss / d logit of the tile's
-// rows (the fused train kernel) instead of A.g; `htop` (nullable): the top layer's output tile still in LDS
-// ([16][rs_h], the fused train kernel) instead of its saved copy in global memory
-__device__ __forceinline__ void mlp_bwd_body(const MlpArgs& A, float* smem, const float* g_lds, const float* htop,
-                                             int rs_h, unsigned long long* tr) {
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int b0 = blockIdx.x * kTM;
-  const int rs = A.rsd;
-  float* d0 = smem;
-  float* d1 = d0 + kTM * rs;
-  const int top = A.n_layers - 1;
-  MLP_TRACE(tr, 0);
-  {
-    // d loss / d pre-activation of the top layer.  Four elements per thread and round trip, every load unconditional
-    // from a clamped address (this loop was one round trip per element: 3.5 us for 16 x 128 -- round 3)
-    const LayerDev& Lt = A.L[top];
-    const int Np = round_up(Lt.N, 16);
-    const int n_e = kTM * Np;
-    const int64_t blast = A.B - 1;
-    for (int e0 = 0; e0 < n_e; e0 += 4 * kT) {
-      float gv[4], hv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int e = e0 + i * kT + tid;
-        e = e < n_e ? e : n_e - 1;
-        const int r = e / Np, n = e - r * Np;
-        const int nn = n < Lt.N ? n : Lt.N - 1;
-        const int64_t b = (b0 + r) < blast ? (b0 + r) : blast;
-        if (A.w_out) gv[i] = (g_lds ? g_lds[r] : ldg_f32(A.g + b)) * ldg_f32(A.w_out + nn);
-        else gv[i] = ldg_f32(A.g + b * A.ldg + nn);
-        hv[i] = htop ? htop[r * rs_h + nn] : ldg_f32(Lt.h + b * Lt.ldh + nn);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int e = e0 + i * kT + tid;
-        if (e < n_e) {
-          const int r = e / Np, n = e - r * Np;
-          const int64_t b = b0 + r;
-          float v = 0.f;
-          if (b < A.B && n < Lt.N) {
-            v = gv[i];
-            if (Lt.relu) v = hv[i] > 0.f ? v : 0.f;
-            if (Lt.dh) stg_f32(Lt.dh + b * Lt.ldh + n, v);
-          }
-          d0[r * rs + n] = v;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  MLP_TRACE(tr, 1);
-  float* din = d0;
-  float* dout = d1;
-  for (int l = top; l >= 0; --l) {
-    const LayerDev& Ld = A.L[l];
-    if (l > 0 || A.gx) {
-      if (Ld.K <= 32 * kWaves) {
-        const int ngroups = (Ld.K + 31) >> 5;
-        for (int gb = wv; gb < ngroups; gb += kWaves) bwd_cols<2>(A, l, din, dout, rs, gb, b0, g, c);
-      } else {
-        const int ngroups = (Ld.K + 63) >> 6;
-        for (int gb = wv; gb < ngroups; gb += kWaves) bwd_cols<4>(A, l, din, dout, rs, gb, b0, g, c);
-      }
-    }
-    MLP_TRACE(tr, 2 + 2 * (top - l));
-    __syncthreads();
-    MLP_TRACE(tr, 3 + 2 * (top - l));
-    float* t = din;
-    din = dout;
-    dout = t;
-  }
-  MLP_TRACE(tr, 15);
-}
-
 
 // ------------------------------------------------------------------------------------------------------------
 // fast path (round 3): towers whose layers are at most 512 wide and whose input is one staged chunk -- every
@@ -1543,6 +1009,21 @@ __device__ __forceinline__ void mlp_bwd_fast(const MlpArgs& A, float* smem, cons
   else mlp_bwd_fast_q<4>(A, smem, g_lds, hb0, hb1, rs_h FT_PASS);
 }
 
+__global__ __launch_bounds__(kT) void k_mlp_fwd(MlpArgs A) {
+  extern __shared__ __align__(16) float smem[];
+  FT_DECL;
+#ifdef DCTR_FAST_ONLY   // (ISA reading aid: compile the fast body alone)
+  mlp_fwd_fast<false>(A, smem, nullptr, GatherArgs{}, nullptr, nullptr FT_PASS);
+#else
+  if (A.fast) {
+    mlp_fwd_fast<false>(A, smem, nullptr, GatherArgs{}, nullptr, nullptr FT_PASS);
+    FT_FLUSH(A.trace);
+  } else {
+    mlp_fwd_body<false>(A, smem, nullptr);
+  }
+#endif
+}
+
 __global__ __launch_bounds__(kT) void k_mlp_bwd_data(MlpArgs A) {
   extern __shared__ __align__(16) float smem[];
   FT_DECL;
@@ -1551,489 +1032,6 @@ __global__ __launch_bounds__(kT) void k_mlp_bwd_data(MlpArgs A) {
     FT_FLUSH(A.trace);
   } else {
     mlp_bwd_body(A, smem, nullptr, nullptr, 0, A.trace);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// CrossNet, matrix form: backward-data of a 16-sample row tile through all layers
-// ------------------------------------------------------------------------------------------------------------
-// With g = d loss / d x_{l+1}:   a_l = g (.) x_0  (= d loss / d u_l: what the weight-gradient kernel consumes, stored in
-// the layer's `dh`, over the u_l the forward parked there);   d loss / d x_l = g + a_l W_l;   and x_0 collects
-// sum_l g (.) u_l on the side (kept in registers: a thread owns the same elements of the tile in every layer).
-// LDS: x_0 | g (ping) | g (pong) | a_l, [16][rs] floats each.
-__global__ __launch_bounds__(kT) void k_cross_mat_bwd(MlpArgs A) {
-  extern __shared__ __align__(16) float smem[];
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int b0 = blockIdx.x * kTM;
-  const int rs = A.rsd;
-  const int W = A.L[0].K;
-  const int Wp = round_up(W, 16);
-  float* x0s = smem;
-  float* gin = x0s + kTM * rs;
-  float* gout = gin + kTM * rs;
-  float* as = gout + kTM * rs;
-  constexpr int kPer = kTM * kKC / kT;      // elements of the tile a thread owns (W <= kKC; unrolled: registers)
-  float side[kPer];
-#pragma unroll
-  for (int k = 0; k < kPer; ++k) side[k] = 0.f;
-  const int n_el = kTM * Wp;
-  for (int e = tid; e < n_el; e += kT) {
-    const int r = e / Wp, n = e - r * Wp;
-    const int64_t b = b0 + r;
-    const bool ok = b < A.B && n < W;
-    x0s[r * rs + n] = ok ? ldg_f32(A.x + b * A.ldx + n) : 0.f;
-    gin[r * rs + n] = ok ? ldg_f32(A.g + b * A.ldg + n) : 0.f;
-  }
-  __syncthreads();
-  for (int l = A.n_layers - 1; l >= 0; --l) {
-    const LayerDev& Ld = A.L[l];
-    // a_l = g (.) x_0 -> LDS (the A operand) and the layer's dh (over u_l, which feeds the side term first)
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int e = tid + k * kT;
-      if (e < n_el) {
-        const int r = e / Wp, n = e - r * Wp;
-        const int64_t b = b0 + r;
-        const float gv = gin[r * rs + n];
-        const float av = gv * x0s[r * rs + n];
-        as[r * rs + n] = av;
-        if (b < A.B && n < W) {
-          float* up = Ld.dh + b * Ld.ldh + n;
-          side[k] += gv * ldg_f32(up);
-          stg_f32(up, av);
-        }
-      }
-    }
-    __syncthreads();
-    // d loss / d x_l = g + a_l W_l : 64-column groups over the waves, reduction over n (rows of W_l)
-    const int ngroups = (W + 63) >> 6;
-    for (int gb = wv; gb < ngroups; gb += kWaves) {
-      const int col0 = 64 * gb + 4 * c;
-      const int colc = col0 < Ld.ldw ? col0 : 0;
-      f32x4 acc[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* ap = as + c * rs + 4 * g;
-      const int n_it = Wp >> 4;
-      const DCTR_GLOBAL char* wbase = (const DCTR_GLOBAL char*)Ld.W;
-      const uint32_t ldw4 = static_cast<uint32_t>(Ld.ldw) * 4u;
-      const uint32_t vlast = static_cast<uint32_t>(Ld.N - 1) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-      uint32_t vrow[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) vrow[j] = static_cast<uint32_t>(4 * g + j) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-      auto wld = [&](int it, f32x4* dst) {
-        it = it < n_it ? it : n_it - 1;
-        const uint32_t so = static_cast<uint32_t>(it) * 16u * ldw4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          uint32_t o = vrow[j] + so;
-          o = o < vlast ? o : vlast;                                  // rows past N re-read row N-1 (A is 0 there)
-          dst[j] = *(const DCTR_GLOBAL f32x4*)(wbase + o);
-        }
-      };
-      constexpr int PD = 5;
-      f32x4 ring[PD][4];
-#pragma unroll
-      for (int d = 0; d < PD - 1; ++d) wld(d, ring[d]);
-      const int n_grp = n_it / PD, rem = n_it - n_grp * PD;
-      f32x4 a_nxt = *reinterpret_cast<const f32x4*>(ap);
-      for (int gi = 0; gi < n_grp; ++gi) {
-#pragma unroll
-        for (int d = 0; d < PD; ++d) {
-          const int it = gi * PD + d;
-          wld(it + PD - 1, ring[(d + PD - 1) % PD]);
-          const f32x4 a4 = a_nxt;
-          const int itn = it + 1 < n_it ? it + 1 : it;
-          a_nxt = *reinterpret_cast<const f32x4*>(ap + (itn << 4));
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < PD - 1; ++d) {
-        if (d < rem) {
-          const int it = n_grp * PD + d;
-          const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + (it << 4));
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-        }
-      }
-      if (col0 < Wp) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 4 * g + r;
-          f32x4 v = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-          const f32x4 gprev = *reinterpret_cast<const f32x4*>(gin + row * rs + col0);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = (col0 + q < W) ? v[q] + gprev[q] : 0.f;
-          *reinterpret_cast<f32x4*>(gout + row * rs + col0) = v;
-        }
-      }
-    }
-    __syncthreads();
-    float* t = gin;
-    gin = gout;
-    gout = t;
-  }
-  // d loss / d x_0 = what came down the chain + the side term
-  if (A.gx) {
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int e = tid + k * kT;
-      if (e < n_el) {
-        const int r = e / Wp, n = e - r * Wp;
-        const int64_t b = b0 + r;
-        if (b < A.B && n < A.ldgx) stg_f32(A.gx + b * A.ldgx + n, n < W ? gin[r * rs + n] + side[k] : 0.f);
-      }
-    }
-    // columns [Wp, ldgx) of gx (padding) are written as zeros as well, however wide the padding is
-    const int xp = static_cast<int>(A.ldgx) - Wp;
-    for (int e = tid; e < kTM * xp; e += kT) {
-      const int r = e / xp, n = Wp + (e - r * xp);
-      const int64_t b = b0 + r;
-      if (b < A.B) stg_f32(A.gx + b * A.ldgx + n, 0.f);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// CrossNetMix (DCN-Mix): mixture of low-rank experts per cross layer, as three dense layers each (see dctr.h)
-// ------------------------------------------------------------------------------------------------------------
-// one dense layer of a 16-sample tile whose input sits in LDS: bias-initialised accumulators, the forward's MFMA
-// loops, then epi(row, n, value) per output element
-template <typename Epi>
-__device__ __forceinline__ void mix_layer(const LayerDev& Ld, const float* in, int rs, int klen, int wv, int g, int c,
-                                          Epi epi) {
-  const int ntile = (Ld.N + 15) >> 4;
-  for (int tbase = 0; tbase < ntile; tbase += kWaves * kNTMax) {
-    const int tile0 = tbase + wv;
-    int nt = 0;
-#pragma unroll
-    for (int t = 0; t < kNTMax; ++t) nt += (tile0 + t * kWaves < ntile) ? 1 : 0;
-    f32x4 acc[kNTMax];
-#pragma unroll
-    for (int t = 0; t < kNTMax; ++t) {
-      const int n = (tile0 + t * kWaves) * 16 + c;
-      const float bv = (t < nt && n < Ld.N && Ld.bias) ? ldg_f32(Ld.bias + n) : 0.f;
-      acc[t] = f32x4{bv, bv, bv, bv};
-    }
-    fwd_dispatch(nt, in, rs, 0, klen, Ld, tile0, acc, g, c, []() {});
-#pragma unroll
-    for (int t = 0; t < kNTMax; ++t) {
-      if (t < nt) {
-        const int n = (tile0 + t * kWaves) * 16 + c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) epi(4 * g + r, n, acc[t][r]);
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(kT) void k_cross_mix_fwd(MlpArgs A, int E, int R) {
-  extern __shared__ __align__(16) float smem[];
-  __shared__ float sc[kTM][8];
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int b0 = blockIdx.x * kTM;
-  const int W = A.L[0].K, Wp = round_up(W, 16);
-  const int ER = E * R, N1 = ER + E;
-  const int rsw = Wp + 4, rsv = round_up(N1, 16) + 4;
-  float* xs = smem;                 // x_0
-  float* xa = xs + kTM * rsw;       // x_l / x_{l+1}: ping
-  float* xb = xa + kTM * rsw;       //                pong
-  float* v1 = xb + kTM * rsw;       // [v1 | scores]
-  float* v2 = v1 + kTM * rsv;       // s (.) v2
-  for (int e = tid; e < kTM * Wp; e += kT) {
-    const int r = e / Wp, n = e - r * Wp;
-    const int64_t b = b0 + r;
-    xs[r * rsw + n] = (b < A.B && n < W) ? ldg_f32(A.x + b * A.ldx + n) : 0.f;
-  }
-  __syncthreads();
-  const float* xl = xs;
-  float* xn = xa;
-  const int n_cross = A.n_layers / 3;
-  for (int lc = 0; lc < n_cross; ++lc) {
-    const LayerDev& L1 = A.L[3 * lc];
-    const LayerDev& L2 = A.L[3 * lc + 1];
-    const LayerDev& L3 = A.L[3 * lc + 2];
-    // ---- project to the experts' rank spaces (+ the gating scores as E more output columns)
-    mix_layer(L1, xl, rsw, Wp, wv, g, c, [&](int row, int n, float v) {
-      // (the scores go to their own array: the next layer reads v1 over round16(E*R) columns and whatever sits
-      // beyond E*R must be zero -- its weight loads are pulled back inside the row there)
-      if (n >= ER && n < N1) sc[row][n - ER] = v;
-      v = (n < ER) ? tanhf(v) : 0.f;
-      v1[row * rsv + n] = v;
-      if (n < ER && b0 + row < A.B) stg_f32(L1.h + static_cast<int64_t>(b0 + row) * L1.ldh + n, v);
-    });
-    __syncthreads();
-    if (tid < kTM) {                                     // softmax over the E scores of a sample (torch.softmax, dim=1)
-      float m = -INFINITY;
-      for (int i = 0; i < E; ++i) m = fmaxf(m, sc[tid][i]);
-      float ex[8], sum = 0.f;
-      for (int i = 0; i < E; ++i) {
-        ex[i] = expf(sc[tid][i] - m);
-        sum += ex[i];
-      }
-      for (int i = 0; i < E; ++i) {
-        const float si = ex[i] / sum;
-        sc[tid][i] = si;
-        if (b0 + tid < A.B) stg_f32(L1.h + static_cast<int64_t>(b0 + tid) * L1.ldh + ER + i, si);
-      }
-    }
-    __syncthreads();
-    // ---- the experts' r x r maps (one block-diagonal layer); the mixture weights go onto the result
-    mix_layer(L2, v1, rsv, round_up(ER, 16), wv, g, c, [&](int row, int n, float v) {
-      float t = 0.f, ts = 0.f;
-      if (n < ER) {
-        t = tanhf(v);
-        ts = t * sc[row][n / R];
-        if (b0 + row < A.B) {
-          stg_f32(L2.dh + static_cast<int64_t>(b0 + row) * L2.ldh + n, t);     // parked for the backward
-          stg_f32(L2.h + static_cast<int64_t>(b0 + row) * L2.ldh + n, ts);
-        }
-      }
-      v2[row * rsv + n] = ts;
-    });
-    __syncthreads();
-    // ---- back to R^W, bias, cross with x_0, residual
-    mix_layer(L3, v2, rsv, round_up(ER, 16), wv, g, c, [&](int row, int n, float u) {
-      float v = 0.f;
-      if (n < W) {
-        v = xs[row * rsw + n] * u + xl[row * rsw + n];
-        if (b0 + row < A.B) {
-          stg_f32(L3.dh + static_cast<int64_t>(b0 + row) * L3.ldh + n, u);     // parked for the backward
-          stg_f32(L3.h + static_cast<int64_t>(b0 + row) * L3.ldh + n, v);
-        }
-      }
-      xn[row * rsw + n] = v;
-    });
-    __syncthreads();
-    xl = xn;
-    xn = (xn == xa) ? xb : xa;
-  }
-}
-
-// out[row, k] = sum_{n < N} a[row, n] W[n, k] for k in [0, ncols): the backward-data product of one dense layer on a
-// 16-sample tile (a in LDS, zero beyond N); 64-column groups over the waves; epi(row, col0, f32x4) per 4 columns.
-template <typename Epi>
-__device__ __forceinline__ void mix_bwd_product(const float* as, int rs, int Nred, const LayerDev& Ld, int ncols,
-                                                int wv, int g, int c, Epi epi) {
-  const int ngroups = (ncols + 63) >> 6;
-  const int ncp = round_up(ncols, 16);
-  for (int gb = wv; gb < ngroups; gb += kWaves) {
-    const int col0 = 64 * gb + 4 * c;
-    const int colc = col0 < Ld.ldw ? col0 : 0;
-    f32x4 acc[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* ap = as + c * rs + 4 * g;
-    const int n_it = Nred >> 4;
-    const DCTR_GLOBAL char* wbase = (const DCTR_GLOBAL char*)Ld.W;
-    const uint32_t ldw4 = static_cast<uint32_t>(Ld.ldw) * 4u;
-    const uint32_t vlast = static_cast<uint32_t>(Ld.N - 1) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-    uint32_t vrow[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) vrow[j] = static_cast<uint32_t>(4 * g + j) * ldw4 + static_cast<uint32_t>(colc) * 4u;
-    auto wld = [&](int it, f32x4* dst) {
-      it = it < n_it ? it : n_it - 1;
-      const uint32_t so = static_cast<uint32_t>(it) * 16u * ldw4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t o = vrow[j] + so;
-        o = o < vlast ? o : vlast;                                  // rows past N re-read row N-1 (a is 0 there)
-        dst[j] = *(const DCTR_GLOBAL f32x4*)(wbase + o);
-      }
-    };
-    constexpr int PD = 5;
-    f32x4 ring[PD][4];
-#pragma unroll
-    for (int d = 0; d < PD - 1; ++d) wld(d, ring[d]);
-    const int n_grp = n_it / PD, rem = n_it - n_grp * PD;
-    f32x4 a_nxt = *reinterpret_cast<const f32x4*>(ap);
-    for (int gi = 0; gi < n_grp; ++gi) {
-#pragma unroll
-      for (int d = 0; d < PD; ++d) {
-        const int it = gi * PD + d;
-        wld(it + PD - 1, ring[(d + PD - 1) % PD]);
-        const f32x4 a4 = a_nxt;
-        const int itn = it + 1 < n_it ? it + 1 : it;
-        a_nxt = *reinterpret_cast<const f32x4*>(ap + (itn << 4));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < PD - 1; ++d) {
-      if (d < rem) {
-        const int it = n_grp * PD + d;
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + (it << 4));
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[q] = mfma16(a4[j], ring[d][j][q], acc[q]);
-      }
-    }
-    if (col0 < ncp) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) epi(4 * g + r, col0, f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]});
-    }
-  }
-}
-
-// backward-data of a 16-sample tile through all cross layers.  Per layer, with g = d loss / d x_{l+1}:
-//   a3 = g (.) x_0  (-> dh of layer 3l+2, over the parked u; x_0 collects g (.) u on the side)
-//   p3 = a3 W3;  d s_e = sum_r p3[e, r] v2[e, r];  a2 = p3 (.) s_e (.) (1 - v2^2)  (-> dh of layer 3l+1, over the parked v2)
-//   softmax backward: d score_e = s_e (d s_e - sum_e' s_e' d s_e')
-//   a1 = [ (a2 W2) (.) (1 - v1^2) | d score ]  (-> dh of layer 3l);   d loss / d x_l = g + a1 W1
-__global__ __launch_bounds__(kT) void k_cross_mix_bwd(MlpArgs A, int E, int R) {
-  extern __shared__ __align__(16) float smem[];
-  __shared__ float dsc[kTM][8];
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int b0 = blockIdx.x * kTM;
-  const int W = A.L[0].K, Wp = round_up(W, 16);
-  const int ER = E * R, N1 = ER + E;
-  const int ERp = round_up(ER, 16), N1p = round_up(N1, 16);
-  const int rsw = round_up(W, 64) + 4, rsv = round_up(N1, 64) + 4;
-  float* x0s = smem;
-  float* gin = x0s + kTM * rsw;
-  float* gout = gin + kTM * rsw;
-  float* a3 = gout + kTM * rsw;
-  float* p3 = a3 + kTM * rsw;       // [16][rsv]: p3, then a2 in place
-  float* a1 = p3 + kTM * rsv;       // [16][rsv]
-  constexpr int kPer = kTM * kKC / kT;
-  float side[kPer];
-#pragma unroll
-  for (int k = 0; k < kPer; ++k) side[k] = 0.f;
-  const int n_el = kTM * Wp;
-  for (int e = tid; e < n_el; e += kT) {
-    const int r = e / Wp, n = e - r * Wp;
-    const int64_t b = b0 + r;
-    const bool ok = b < A.B && n < W;
-    x0s[r * rsw + n] = ok ? ldg_f32(A.x + b * A.ldx + n) : 0.f;
-    gin[r * rsw + n] = ok ? ldg_f32(A.g + b * A.ldg + n) : 0.f;
-  }
-  for (int e = tid; e < kTM * rsv; e += kT) {
-    p3[e] = 0.f;
-    a1[e] = 0.f;
-  }
-  __syncthreads();
-  const int n_cross = A.n_layers / 3;
-  for (int lc = n_cross - 1; lc >= 0; --lc) {
-    const LayerDev& L1 = A.L[3 * lc];
-    const LayerDev& L2 = A.L[3 * lc + 1];
-    const LayerDev& L3 = A.L[3 * lc + 2];
-    // ---- a3 = g (.) x_0; the side term for x_0
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int e = tid + k * kT;
-      if (e < n_el) {
-        const int r = e / Wp, n = e - r * Wp;
-        const int64_t b = b0 + r;
-        const float gv = gin[r * rsw + n];
-        const float av = gv * x0s[r * rsw + n];
-        a3[r * rsw + n] = av;
-        if (b < A.B && n < W) {
-          float* up = L3.dh + b * L3.ldh + n;
-          side[k] += gv * ldg_f32(up);
-          stg_f32(up, av);
-        }
-      }
-    }
-    __syncthreads();
-    // ---- p3 = a3 W3  ([16, W] x [W, ER])
-    mix_bwd_product(a3, rsw, Wp, L3, ER, wv, g, c, [&](int row, int col0, f32x4 v) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) p3[row * rsv + col0 + q] = (col0 + q < ER) ? v[q] : 0.f;
-    });
-    __syncthreads();
-    // ---- d s_e (a reduction over the expert's R columns), then a2 in place
-    if (tid < kTM * E) {
-      const int row = tid / E, e = tid - row * E;
-      const int64_t b = b0 + row;
-      float acc = 0.f;
-      if (b < A.B)
-        for (int r = 0; r < R; ++r) acc += p3[row * rsv + e * R + r] * ldg_f32(L2.dh + b * L2.ldh + e * R + r);
-      dsc[row][e] = acc;
-    }
-    __syncthreads();
-    for (int e = tid; e < kTM * ERp; e += kT) {
-      const int row = e / ERp, n = e - row * ERp;
-      const int64_t b = b0 + row;
-      float av = 0.f;
-      if (b < A.B && n < ER) {
-        const float t = ldg_f32(L2.dh + b * L2.ldh + n);                     // unscaled v2 (parked by the forward)
-        const float s = ldg_f32(L1.h + b * L1.ldh + ER + n / R);
-        av = p3[row * rsv + n] * s * (1.f - t * t);
-        stg_f32(L2.dh + b * L2.ldh + n, av);
-      }
-      p3[row * rsv + n] = av;
-    }
-    if (tid < kTM) {                                                          // softmax backward
-      const int64_t b = b0 + tid;
-      float dot = 0.f, sv[8];
-      for (int i = 0; i < E; ++i) {
-        sv[i] = b < A.B ? ldg_f32(L1.h + b * L1.ldh + ER + i) : 0.f;
-        dot += sv[i] * dsc[tid][i];
-      }
-      for (int i = 0; i < E; ++i) {
-        const float ds = sv[i] * (dsc[tid][i] - dot);
-        a1[tid * rsv + ER + i] = ds;
-        if (b < A.B) stg_f32(L1.dh + b * L1.ldh + ER + i, ds);
-      }
-    }
-    __syncthreads();
-    // ---- a1[:, :ER] = (a2 W2) (.) (1 - v1^2)
-    mix_bwd_product(p3, rsv, ERp, L2, ER, wv, g, c, [&](int row, int col0, f32x4 v) {
-      const int64_t b = b0 + row;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = col0 + q;
-        float av = 0.f;
-        if (b < A.B && n < ER) {
-          const float t = ldg_f32(L1.h + b * L1.ldh + n);
-          av = v[q] * (1.f - t * t);
-          stg_f32(L1.dh + b * L1.ldh + n, av);
-        }
-        if (n < ER) a1[row * rsv + n] = av;
-      }
-    });
-    __syncthreads();
-    // ---- d loss / d x_l = g + a1 W1  ([16, N1] x [N1, W])
-    mix_bwd_product(a1, rsv, N1p, L1, W, wv, g, c, [&](int row, int col0, f32x4 v) {
-      const f32x4 gprev = *reinterpret_cast<const f32x4*>(gin + row * rsw + col0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = (col0 + q < W) ? v[q] + gprev[q] : 0.f;
-      *reinterpret_cast<f32x4*>(gout + row * rsw + col0) = v;
-    });
-    __syncthreads();
-    float* t = gin;
-    gin = gout;
-    gout = t;
-  }
-  if (A.gx) {
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int e = tid + k * kT;
-      if (e < n_el) {
-        const int r = e / Wp, n = e - r * Wp;
-        const int64_t b = b0 + r;
-        if (b < A.B && n < A.ldgx) stg_f32(A.gx + b * A.ldgx + n, n < W ? gin[r * rsw + n] + side[k] : 0.f);
-      }
-    }
-    for (int e = tid; e < kTM * 4; e += kT) {
-      const int r = e >> 2, n = Wp + (e & 3);
-      const int64_t b = b0 + r;
-      if (b < A.B && n < A.ldgx) stg_f32(A.gx + b * A.ldgx + n, 0.f);
-    }
   }
 }
 
@@ -2489,27 +1487,6 @@ __global__ __launch_bounds__(256) void k_mlp_reduce(ReduceArgs A) {
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------------------
-int check_mlp(const dctr_mlp_t* m, int32_t B) {
-  if (!m || B < 0 || m->n_layers <= 0 || m->n_layers > kMaxL) return DCTR_EINVAL;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& L = m->layer[l];
-    if (!L.W || L.K <= 0 || L.N <= 0 || L.ld_w < L.K) return DCTR_EINVAL;
-    if (L.ld_w % 4 != 0 || reinterpret_cast<uintptr_t>(L.W) % 16 != 0) return DCTR_EALIGN;
-    if (l > 0 && L.K != m->layer[l - 1].N) return DCTR_EINVAL;
-    if (L.N > 2048) return DCTR_ENOSUP;
-    if (static_cast<int64_t>(L.N) * L.ld_w * 4 >= (int64_t(1) << 31)) return DCTR_ENOSUP;  // 32-bit weight offsets
-  }
-  return DCTR_OK;
-}
-
-void fill_layers(const dctr_mlp_t* m, LayerDev* L) {
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& s = m->layer[l];
-    L[l].W = s.W; L[l].bias = s.bias; L[l].h = s.h; L[l].dh = s.dh;
-    L[l].K = s.K; L[l].N = s.N; L[l].ldw = s.ld_w; L[l].ldh = s.ld_h; L[l].relu = s.relu;
-  }
-}
-
 // Columns of the tower input staged at a time: as many as leave room for the two activation tiles of the widest layer
 // (1024-wide towers: 256; the chunk only bounds how often the first layer's K loop re-stages).
 int pick_kc(int K0p, int rsh) {
@@ -2538,17 +1515,15 @@ uint32_t diag_wmask() {
   return 0xffffffffu;
 }
 
-int max_width(const dctr_mlp_t* m) {
-  int w = 0;
-  for (int l = 0; l < m->n_layers; ++l) w = m->layer[l].N > w ? m->layer[l].N : w;
-  return w;
+int bwd_stride(const dctr_mlp_t* m) {
+  int w = max_width(m);
+  for (int l = 1; l < m->n_layers; ++l) w = m->layer[l].K > w ? m->layer[l].K : w;
+  return round_up(w, 64) + kPad;
 }
 
-struct WgradPlan {
-  int S, bs, P, pbs;
-  int blk0[kMaxL + 2];
-  int64_t off_w[kMaxL], off_b[kMaxL], off_o, slab;
-};
+}  // namespace
+
+namespace dctr {
 
 WgradPlan plan_wgrad(const dctr_mlp_t* m, int32_t B) {
   WgradPlan P;
@@ -2613,74 +1588,6 @@ WgradPlan plan_wgrad(const dctr_mlp_t* m, int32_t B) {
   return P;
 }
 
-}  // namespace
-
-// diagnostics: buf holds 3 x 4096 x 16 u64 (forward | backward-data | wgrad workgroups); NULL switches it off
-#ifdef DCTR_DIAG
-extern "C" void dctr_dbg_mlp_trace(unsigned long long* buf) { g_mlp_trace = buf; }
-#endif
-
-extern "C" int dctr_mlp_fwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, float* logit,
-                            dctr_stream_t stream) {
-  const int rc = check_mlp(m, B);
-  if (rc != DCTR_OK) return rc;
-  if (!x || ld_x < m->layer[0].K) return DCTR_EINVAL;
-  if (ld_x % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return DCTR_EALIGN;
-  if (m->w_out && !logit) return DCTR_EINVAL;
-  if (!m->w_out && !m->layer[m->n_layers - 1].h) return DCTR_EINVAL;  // nowhere to put the result
-  for (int l = 0; l < m->n_layers; ++l)
-    if (m->layer[l].h && (m->layer[l].ld_h < m->layer[l].N)) return DCTR_EINVAL;
-  if (B == 0) return DCTR_OK;
-  MlpArgs a;
-  fill_layers(m, a.L);
-  a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = m->w_out; a.logit = logit;
-  a.g = nullptr; a.ldg = 0; a.gx = nullptr; a.ldgx = 0;
-  a.trace = g_mlp_trace;
-  const int K0p = round_up(m->layer[0].K, 16);
-  a.rsh = round_up(max_width(m), 16) + kPad;
-  a.kc = pick_kc(K0p, a.rsh);
-  a.rsx = (K0p < a.kc ? K0p : a.kc) + kPad;
-  a.rsd = 0;
-  a.fast = tower_fast(m, a.kc); a.wmask = diag_wmask();
-  const size_t lds = static_cast<size_t>(kTM) * (a.rsx + 2 * a.rsh) * 4;
-  if (lds > 150 * 1024) return DCTR_ENOSUP;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-  k_mlp_fwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, static_cast<hipStream_t>(stream)>>>(a);
-  return launch_status();
-}
-
-extern "C" size_t dctr_mlp_bwd_workspace_floats(const dctr_mlp_t* m, int32_t B) {
-  if (check_mlp(m, B) != DCTR_OK) return 0;
-  const WgradPlan P = plan_wgrad(m, B);
-  return static_cast<size_t>(P.slab) * P.S;
-}
-
-namespace {
-
-int check_bwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, const float* gx, int64_t ld_gx) {
-  if (!x || ld_x < m->layer[0].K) return DCTR_EINVAL;
-  if (gx && (ld_gx < m->layer[0].K)) return DCTR_EINVAL;
-  if (gx && (ld_gx % 4 != 0 || reinterpret_cast<uintptr_t>(gx) % 16 != 0)) return DCTR_EALIGN;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& L = m->layer[l];
-    if (!L.h || !L.dh || L.ld_h < L.N) return DCTR_EINVAL;
-    if (L.ld_h % 4 != 0 || reinterpret_cast<uintptr_t>(L.h) % 16 != 0 || reinterpret_cast<uintptr_t>(L.dh) % 16 != 0)
-      return DCTR_EALIGN;
-    // k_mlp_wgrad addresses its operands with 32-bit byte offsets
-    if (static_cast<int64_t>(B) * L.ld_h * 4 >= (int64_t(1) << 32)) return DCTR_ENOSUP;
-  }
-  if (static_cast<int64_t>(B) * ld_x * 4 >= (int64_t(1) << 32)) return DCTR_ENOSUP;
-  return DCTR_OK;
-}
-
-int bwd_stride(const dctr_mlp_t* m) {
-  int w = max_width(m);
-  for (int l = 1; l < m->n_layers; ++l) w = m->layer[l].K > w ? m->layer[l].K : w;
-  return round_up(w, 64) + kPad;
-}
-
 // weight gradients (split-batch partials) + their fixed-order reduction (+ the head's partials, fused step only)
 int launch_wgrad_reduce(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, const float* g,
                         float* workspace, const float* head_loss, const float* head_gbias, int n_head, float* loss,
@@ -2726,7 +1633,47 @@ int launch_wgrad_reduce(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32
   return launch_status();
 }
 
-}  // namespace
+}  // namespace dctr
+
+// diagnostics: buf holds 3 x 4096 x 16 u64 (forward | backward-data | wgrad workgroups); NULL switches it off
+#ifdef DCTR_DIAG
+unsigned long long* dctr::g_mlp_trace = nullptr;
+extern "C" void dctr_dbg_mlp_trace(unsigned long long* buf) { g_mlp_trace = buf; }
+#endif
+
+extern "C" int dctr_mlp_fwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, float* logit,
+                            dctr_stream_t stream) {
+  const int rc = check_mlp(m, B);
+  if (rc != DCTR_OK) return rc;
+  if (!x || ld_x < m->layer[0].K) return DCTR_EINVAL;
+  if (ld_x % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return DCTR_EALIGN;
+  if (m->w_out && !logit) return DCTR_EINVAL;
+  if (!m->w_out && !m->layer[m->n_layers - 1].h) return DCTR_EINVAL;  // nowhere to put the result
+  for (int l = 0; l < m->n_layers; ++l)
+    if (m->layer[l].h && (m->layer[l].ld_h < m->layer[l].N)) return DCTR_EINVAL;
+  if (B == 0) return DCTR_OK;
+  MlpArgs a = mlp_args(m, B, x, ld_x);
+  a.w_out = m->w_out; a.logit = logit;
+  a.trace = g_mlp_trace;
+  const int K0p = round_up(m->layer[0].K, 16);
+  a.rsh = round_up(max_width(m), 16) + kPad;
+  a.kc = pick_kc(K0p, a.rsh);
+  a.rsx = (K0p < a.kc ? K0p : a.kc) + kPad;
+  a.fast = tower_fast(m, a.kc); a.wmask = diag_wmask();
+  const size_t lds = static_cast<size_t>(kTM) * (a.rsx + 2 * a.rsh) * 4;
+  if (lds > 150 * 1024) return DCTR_ENOSUP;
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(lds));
+  k_mlp_fwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, static_cast<hipStream_t>(stream)>>>(a);
+  return launch_status();
+}
+
+extern "C" size_t dctr_mlp_bwd_workspace_floats(const dctr_mlp_t* m, int32_t B) {
+  if (check_mlp(m, B) != DCTR_OK) return 0;
+  const WgradPlan P = plan_wgrad(m, B);
+  return static_cast<size_t>(P.slab) * P.S;
+}
 
 extern "C" int dctr_mlp_bwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, const float* g,
                             int64_t ld_g, float* gx, int64_t ld_gx, float* workspace, dctr_stream_t stream) {
@@ -2739,12 +1686,10 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, i
   if (B == 0) return DCTR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   {
-    MlpArgs a;
-    fill_layers(m, a.L);
-    a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = m->w_out; a.logit = nullptr;
+    MlpArgs a = mlp_args(m, B, x, ld_x);
+    a.w_out = m->w_out;
     a.g = g; a.ldg = ld_g; a.gx = gx; a.ldgx = ld_gx;
     a.trace = g_mlp_trace ? g_mlp_trace + 16ull * 4096 : nullptr;
-    a.rsx = 0; a.rsh = 0;
     a.rsd = bwd_stride(m);
     a.fast = tower_fast(m, kKC); a.wmask = diag_wmask();
     const size_t lds = static_cast<size_t>(kTM) * 2 * a.rsd * 4;
@@ -2782,10 +1727,8 @@ extern "C" int dctr_mlp_train_step(const dctr_mlp_t* m, const float* x, int64_t 
   float* part_loss = workspace + static_cast<size_t>(P.slab) * P.S;
   float* part_gb = part_loss + n_tiles;
   {
-    MlpArgs a;
-    fill_layers(m, a.L);
-    a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = m->w_out; a.logit = nullptr;
-    a.g = nullptr; a.ldg = 0; a.gx = gx; a.ldgx = ld_gx;
+    MlpArgs a = mlp_args(m, B, x, ld_x);
+    a.w_out = m->w_out; a.gx = gx; a.ldgx = ld_gx;
     a.trace = g_mlp_trace;
     const int K0p = round_up(m->layer[0].K, 16);
     a.rsh = round_up(max_width(m), 16) + kPad;
@@ -2825,9 +1768,8 @@ struct TrainGeom {
 };
 int train_geom(const dctr_mlp_t* m, int32_t B, TrainGeom* T) {
   MlpArgs& a = T->a;
-  fill_layers(m, a.L);
-  a.n_layers = m->n_layers; a.B = B; a.w_out = m->w_out; a.logit = nullptr;
-  a.g = nullptr; a.ldg = 0;
+  a = mlp_args(m, B, nullptr, 0);   // (the step sets x and gx)
+  a.w_out = m->w_out;
   a.trace = g_mlp_trace;
   const int K0p = round_up(m->layer[0].K, 16);
   a.rsh = round_up(max_width(m), 16) + kPad;
@@ -2957,191 +1899,4 @@ extern "C" int dctr_mlp_train_wgrad(const dctr_mlp_t* m, const float* x, int64_t
   float* part_gb = part_loss + n_tiles;
   return launch_wgrad_reduce(m, x, ld_x, B, g_logit, workspace, part_loss, part_gb, n_tiles, loss, g_bias, step,
                              static_cast<hipStream_t>(stream));
-}
-
-// ---- CrossNet, matrix parameterisation (interaction.py:448-451) ------------------------------------------------------
-namespace {
-int check_cross(const dctr_mlp_t* m, int32_t B) {
-  const int rc = check_mlp(m, B);
-  if (rc != DCTR_OK) return rc;
-  if (m->w_out) return DCTR_EINVAL;
-  const int W = m->layer[0].K;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& L = m->layer[l];
-    if (L.K != W || L.N != W || !L.h || !L.dh || L.ld_h < W) return DCTR_EINVAL;
-    if (L.ld_h % 4 != 0 || reinterpret_cast<uintptr_t>(L.h) % 16 != 0 || reinterpret_cast<uintptr_t>(L.dh) % 16 != 0)
-      return DCTR_EALIGN;
-  }
-  return DCTR_OK;
-}
-}  // namespace
-
-extern "C" int dctr_crossnet_mat_supported(int32_t W, int32_t n_layers) {
-  if (W <= 0 || n_layers <= 0 || n_layers > kMaxL) return 0;
-  const int Wp = round_up(W, 16);
-  if (Wp > kKC) return 0;                                              // the forward keeps x_0 as ONE staged chunk
-  const size_t lds_f = static_cast<size_t>(kTM) * ((Wp + 4) + 2 * (Wp + 4)) * 4;
-  const size_t lds_b = static_cast<size_t>(kTM) * 4 * (round_up(W, 64) + 4) * 4;
-  return (lds_f <= 150 * 1024 && lds_b <= 150 * 1024) ? 1 : 0;
-}
-
-extern "C" int dctr_crossnet_mat_fwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B,
-                                     dctr_stream_t stream) {
-  const int rc = check_cross(m, B);
-  if (rc != DCTR_OK) return rc;
-  const int W = m->layer[0].K;
-  if (!x || ld_x < W) return DCTR_EINVAL;
-  if (ld_x % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return DCTR_EALIGN;
-  if (!dctr_crossnet_mat_supported(W, m->n_layers)) return DCTR_ENOSUP;
-  if (B == 0) return DCTR_OK;
-  MlpArgs a;
-  fill_layers(m, a.L);
-  a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = nullptr; a.logit = nullptr;
-  a.g = nullptr; a.ldg = 0; a.gx = nullptr; a.ldgx = 0; a.trace = nullptr;
-  const int Wp = round_up(W, 16);
-  a.kc = kKC;
-  a.rsx = Wp + kPad;
-  a.rsh = Wp + kPad;
-  a.rsd = 0;
-  a.fast = 0; a.wmask = 0xffffffffu;
-  const size_t lds = static_cast<size_t>(kTM) * (a.rsx + 2 * a.rsh) * 4;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cross_mat_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-  k_cross_mat_fwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, static_cast<hipStream_t>(stream)>>>(a);
-  return launch_status();
-}
-
-extern "C" size_t dctr_crossnet_mat_bwd_workspace_floats(const dctr_mlp_t* m, int32_t B) {
-  if (check_mlp(m, B) != DCTR_OK) return 0;
-  const WgradPlan P = plan_wgrad(m, B);
-  return static_cast<size_t>(P.slab) * P.S;
-}
-
-extern "C" int dctr_crossnet_mat_bwd(const dctr_mlp_t* m, const float* x, int64_t ld_x, int32_t B, const float* gY,
-                                     int64_t ld_g, float* gx, int64_t ld_gx, float* workspace, dctr_stream_t stream) {
-  const int rc = check_cross(m, B);
-  if (rc != DCTR_OK) return rc;
-  const int W = m->layer[0].K;
-  if (!x || !gY || !workspace || ld_x < W || ld_g < W) return DCTR_EINVAL;
-  // (as the forward: k_mlp_wgrad reads layer 0's input in column pairs and counts on ld_x % 4 == 0)
-  if (ld_x % 4 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0) return DCTR_EALIGN;
-  const int rb = check_bwd(m, x, ld_x, B, gx, ld_gx);
-  if (rb != DCTR_OK) return rb;
-  if (!dctr_crossnet_mat_supported(W, m->n_layers)) return DCTR_ENOSUP;
-  if (B == 0) return DCTR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  {
-    MlpArgs a;
-    fill_layers(m, a.L);
-    a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = nullptr; a.logit = nullptr;
-    a.g = gY; a.ldg = ld_g; a.gx = gx; a.ldgx = ld_gx; a.trace = nullptr;
-    a.rsx = 0; a.rsh = 0; a.fast = 0; a.wmask = 0xffffffffu;
-    a.rsd = round_up(W, 64) + kPad;
-    const size_t lds = static_cast<size_t>(kTM) * 4 * a.rsd * 4;
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cross_mat_bwd),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    k_cross_mat_bwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, s>>>(a);
-    const int st = launch_status();
-    if (st != DCTR_OK) return st;
-  }
-  // d W_l = a_l^T x_l, d b_l = column sums of a_l: the tower's weight-gradient kernels, as they are
-  return launch_wgrad_reduce(m, x, ld_x, B, nullptr, workspace, nullptr, nullptr, 0, nullptr, nullptr, nullptr, s);
-}
-
-// ---- CrossNetMix (interaction.py:499-534) -----------------------------------------------------------------------------
-namespace {
-int check_mix(const dctr_mlp_t* m, int32_t E, int32_t R, int32_t B) {
-  // (not check_mlp: the dense layers of a cross layer do not chain by width -- layer 3l+1 reads the first E*R of
-  // layer 3l's E*R + E outputs)
-  if (!m || B < 0 || m->n_layers <= 0 || m->n_layers > kMaxL) return DCTR_EINVAL;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& L = m->layer[l];
-    if (!L.W || L.K <= 0 || L.N <= 0 || L.ld_w < L.K) return DCTR_EINVAL;
-    if (L.ld_w % 4 != 0 || reinterpret_cast<uintptr_t>(L.W) % 16 != 0) return DCTR_EALIGN;
-    if (L.N > 2048) return DCTR_ENOSUP;
-  }
-  if (m->w_out || E <= 0 || R <= 0 || m->n_layers % 3 != 0) return DCTR_EINVAL;
-  const int W = m->layer[0].K, ER = E * R;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const dctr_mlp_layer_t& L = m->layer[l];
-    const int k = l % 3;
-    const int wantK = k == 0 ? W : ER, wantN = k == 0 ? ER + E : (k == 1 ? ER : W);
-    if (L.K != wantK || L.N != wantN || !L.h || !L.dh || L.ld_h < L.N) return DCTR_EINVAL;
-    if (L.ld_h % 4 != 0 || reinterpret_cast<uintptr_t>(L.h) % 16 != 0 || reinterpret_cast<uintptr_t>(L.dh) % 16 != 0)
-      return DCTR_EALIGN;
-  }
-  return DCTR_OK;
-}
-size_t mix_lds_fwd(int W, int N1) {
-  return static_cast<size_t>(kTM) * (3 * (round_up(W, 16) + 4) + 2 * (round_up(N1, 16) + 4)) * 4;
-}
-size_t mix_lds_bwd(int W, int N1) {
-  return static_cast<size_t>(kTM) * (4 * (round_up(W, 64) + 4) + 2 * (round_up(N1, 64) + 4)) * 4;
-}
-}  // namespace
-
-extern "C" int dctr_crossnet_mix_supported(int32_t W, int32_t n_cross_layers, int32_t E, int32_t R) {
-  if (W <= 0 || n_cross_layers <= 0 || 3 * n_cross_layers > kMaxL || E <= 0 || E > 8 || R <= 0) return 0;
-  const int N1 = E * R + E;
-  if (round_up(W, 16) > kKC || N1 > 512) return 0;
-  return (mix_lds_fwd(W, N1) <= 150 * 1024 && mix_lds_bwd(W, N1) <= 150 * 1024) ? 1 : 0;
-}
-
-extern "C" int dctr_crossnet_mix_fwd(const dctr_mlp_t* m, int32_t E, int32_t R, const float* x, int64_t ld_x, int32_t B,
-                                     dctr_stream_t stream) {
-  const int rc = check_mix(m, E, R, B);
-  if (rc != DCTR_OK) return rc;
-  const int W = m->layer[0].K;
-  if (!x || ld_x < W) return DCTR_EINVAL;
-  if (!dctr_crossnet_mix_supported(W, m->n_layers / 3, E, R)) return DCTR_ENOSUP;
-  if (B == 0) return DCTR_OK;
-  MlpArgs a;
-  fill_layers(m, a.L);
-  a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = nullptr; a.logit = nullptr;
-  a.g = nullptr; a.ldg = 0; a.gx = nullptr; a.ldgx = 0; a.trace = nullptr;
-  a.kc = kKC; a.rsx = 0; a.rsh = 0; a.rsd = 0; a.fast = 0; a.wmask = 0xffffffffu;
-  const size_t lds = mix_lds_fwd(W, E * R + E);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cross_mix_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(lds));
-  k_cross_mix_fwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, static_cast<hipStream_t>(stream)>>>(a, E, R);
-  return launch_status();
-}
-
-extern "C" size_t dctr_crossnet_mix_bwd_workspace_floats(const dctr_mlp_t* m, int32_t B) {
-  if (!m || B < 0 || m->n_layers <= 0 || m->n_layers > kMaxL) return 0;
-  const WgradPlan P = plan_wgrad(m, B);
-  return static_cast<size_t>(P.slab) * P.S;
-}
-
-extern "C" int dctr_crossnet_mix_bwd(const dctr_mlp_t* m, int32_t E, int32_t R, const float* x, int64_t ld_x, int32_t B,
-                                     const float* gY, int64_t ld_g, float* gx, int64_t ld_gx, float* workspace,
-                                     dctr_stream_t stream) {
-  const int rc = check_mix(m, E, R, B);
-  if (rc != DCTR_OK) return rc;
-  const int W = m->layer[0].K;
-  if (!x || !gY || !workspace || ld_x < W || ld_g < W) return DCTR_EINVAL;
-  const int rb = check_bwd(m, x, ld_x, B, gx, ld_gx);
-  if (rb != DCTR_OK) return rb;
-  if (!dctr_crossnet_mix_supported(W, m->n_layers / 3, E, R)) return DCTR_ENOSUP;
-  if (B == 0) return DCTR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  {
-    MlpArgs a;
-    fill_layers(m, a.L);
-    a.n_layers = m->n_layers; a.B = B; a.x = x; a.ldx = ld_x; a.w_out = nullptr; a.logit = nullptr;
-    a.g = gY; a.ldg = ld_g; a.gx = gx; a.ldgx = ld_gx; a.trace = nullptr;
-    a.kc = kKC; a.rsx = 0; a.rsh = 0; a.rsd = 0; a.fast = 0; a.wmask = 0xffffffffu;
-    const size_t lds = mix_lds_bwd(W, E * R + E);
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cross_mix_bwd),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    k_cross_mix_bwd<<<dim3((B + kTM - 1) / kTM), dim3(kT), lds, s>>>(a, E, R);
-    const int st = launch_status();
-    if (st != DCTR_OK) return st;
-  }
-  // d W of the three dense layers per cross layer (= packed gV | gG, gC blocks, gU) and d b: the tower's kernels
-  return launch_wgrad_reduce(m, x, ld_x, B, nullptr, workspace, nullptr, nullptr, 0, nullptr, nullptr, nullptr, s);
 }

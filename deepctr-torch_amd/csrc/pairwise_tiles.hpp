@@ -12,10 +12,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kSB = 16;  // samples per workgroup (= MFMA rows)
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ int row_stride(int F, int D) {
   // floats per sample row in LDS; (RS mod 32) == 16 spreads consecutive samples over both bank halves
   int rs = F * D;

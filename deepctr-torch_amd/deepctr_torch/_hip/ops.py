@@ -1416,7 +1416,7 @@ class CrossNetVecFunction(torch.autograd.Function):
 class CrossNetMatFunction(torch.autograd.Function):
     """CrossNet, matrix parameterisation (reference interaction.py:448-451): ``x_{l+1} = x_0 * (x_l W_l^T + b_l) + x_l``
     for all layers in ONE forward launch (16 samples per workgroup, x_0 / x_l in LDS, fp32 MFMA) and, for the backward,
-    one data launch + the tower's weight-gradient kernels (csrc/mlp.hip: dctr_crossnet_mat_fwd / _bwd)."""
+    one data launch + the tower's weight-gradient kernels (csrc/cross_tower.hip: dctr_crossnet_mat_fwd / _bwd)."""
 
     @staticmethod
     def _desc(Wp, ld_w, bias, hs, us, gWs, gbs, W):
@@ -1483,7 +1483,7 @@ class CrossNetMatFunction(torch.autograd.Function):
 class CrossNetMixFunction(torch.autograd.Function):
     """CrossNetMix of DCN-Mix (reference interaction.py:499-534): per cross layer a mixture of low-rank experts,
     ``x_{l+1} = x_0 * (sum_e softmax(x_l G^T)_e * tanh(tanh(x_l V_e) C_e^T) U_e^T + b) + x_l``.  All layers in ONE
-    forward launch (csrc/mlp.hip ``dctr_crossnet_mix_fwd``: three dense fp32-MFMA layers per cross layer on a 16-sample
+    forward launch (csrc/cross_tower.hip ``dctr_crossnet_mix_fwd``: three dense fp32-MFMA layers per cross layer on a 16-sample
     tile kept in LDS) and one backward-data launch + the tower's weight-gradient kernels.  The weights travel packed:
     ``W1 = [V (E*R rows) | G (E rows)] x W``, ``W2 = blockdiag(C_e)``, ``W3[w, e*R + r] = U_e[w, r]``."""
 

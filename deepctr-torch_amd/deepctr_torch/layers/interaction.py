@@ -161,7 +161,7 @@ class InteractingLayer(nn.Module):
 class CrossNetMix(nn.Module):
     """Cross network of DCN-Mix: a mixture of low-rank experts per layer, ``[B, W] -> [B, W]`` (reference
     interaction.py:456-534; same constructor, same ``U_list / V_list / C_list [L, E, ...]``, ``gating.<e>.weight``,
-    ``bias [L, W, 1]`` parameters).  All layers in one fp32-MFMA launch each way (csrc/mlp.hip,
+    ``bias [L, W, 1]`` parameters).  All layers in one fp32-MFMA launch each way (csrc/cross_tower.hip,
     ``dctr_crossnet_mix_*``: three dense layers per cross layer on a 16-sample tile in LDS; up to 512 inputs, 4 cross
     layers, 8 experts); beyond that the batched-einsum formulation on PyTorch-ROCm."""
 
@@ -473,7 +473,7 @@ class CrossNet(nn.Module):
     """Cross network of DCN / DCN-M: ``[B, W] -> [B, W]`` (reference interaction.py:397-453; parameters
     ``kernels [L, W, 1 | W]``, ``bias [L, W, 1]``).  The vector form runs all layers in one wave-per-sample kernel
     (csrc/cross.hip); the matrix form runs all layers in one fp32-MFMA launch that keeps x_0 and x_l of a 16-sample
-    tile in LDS (csrc/mlp.hip, ``dctr_crossnet_mat_*``; up to 512 inputs, wider ones go to hipBLASLt)."""
+    tile in LDS (csrc/cross_tower.hip, ``dctr_crossnet_mat_*``; up to 512 inputs, wider ones go to hipBLASLt)."""
 
     def __init__(self, in_features, layer_num=2, parameterization='vector', seed=1024, device='cpu'):
         super(CrossNet, self).__init__()

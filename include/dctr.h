@@ -824,7 +824,7 @@ int dctr_crossnet_vec_bwd(const float* X, int64_t ld_x, int32_t B, int32_t W, in
                           const float* bias, const float* gY, int64_t ld_g, float* gX, int64_t ld_gx,
                           float* g_kernels, float* g_bias, float* workspace, dctr_stream_t stream);
 
-/* ---- CrossNet, matrix parameterisation (interaction.py:448-451; csrc/mlp.hip, on the tower's MFMA machinery) ------
+/* ---- CrossNet, matrix parameterisation (interaction.py:448-451; csrc/cross_tower.hip, on the tower's MFMA machinery)
  *     x_{l+1} = x_0 (.) (x_l W_l^T + b_l) + x_l ,  l = 0..L-1          W_l = crossnet.kernels[l]  [W, W]
  * described as a dctr_mlp_t (declared below) whose layers are all W x W: layer[l].W (rows ld_w floats apart, ld_w % 4
  * == 0), .bias [W], .h [B, ld_h] receives x_{l+1} (the last one IS the result), .dh [B, ld_h] is scratch shared by
@@ -843,7 +843,7 @@ size_t dctr_crossnet_mat_bwd_workspace_floats(const struct dctr_mlp* m, int32_t 
 int dctr_crossnet_mat_bwd(const struct dctr_mlp* m, const float* x, int64_t ld_x, int32_t B, const float* gY,
                           int64_t ld_g, float* gx, int64_t ld_gx, float* workspace, dctr_stream_t stream);
 
-/* ---- CrossNetMix of DCN-Mix (interaction.py:499-534; csrc/mlp.hip) -------------------------------------------------
+/* ---- CrossNetMix of DCN-Mix (interaction.py:499-534; csrc/cross_tower.hip) ---------------------------------------
  * Per cross layer, with E experts of rank R over W inputs (G = the gating weights [E, W], shared by all layers):
  *     s = softmax(x_l G^T)                      v1_e = tanh(x_l V_e)                  v2_e = tanh(v1_e C_e^T)
  *     x_{l+1} = x_0 (.) (sum_e s_e v2_e U_e^T + b) + x_l

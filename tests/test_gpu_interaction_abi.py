@@ -1,4 +1,4 @@
-"""GPU: the older interaction kernels, and the matrix CrossNet of csrc/mlp.hip (``test_crossnet_mat*``: the rules of the second
+"""GPU: the older interaction kernels, and the matrix CrossNet of csrc/cross_tower.hip (``test_crossnet_mat*``: the rules of the second
 part of interaction_abi's docstring, what each case reaches in the tests' docstrings), through the C ABI at the sizes where
 their launchers switch over (csrc/fm.hip,
 afm.hip, interact.hip, cross.hip and the SENET / inner-product part of pairwise.hip), against float64 on the CPU.
@@ -218,7 +218,7 @@ def test_bilinear_envelope():
         assert float(t.min()) == SENT and float(t.max()) == SENT
 
 
-# ---- CrossNet, matrix parameterisation (csrc/mlp.hip: k_cross_mat_fwd / _bwd + the tower's weight-gradient kernels) --------
+# ---- CrossNet, matrix parameterisation (csrc/cross_tower.hip: k_cross_mat_fwd / _bwd + the tower's weight-gradient kernels) -
 @pytest.mark.parametrize("B,W,L", IA.CROSSNET_MAT_CASES)
 def test_crossnet_mat(B, W, L):
     """the rules of interaction_abi's second part (max|ref| as the scale, guarded 777 / NaN workspace, gW's padding columns
