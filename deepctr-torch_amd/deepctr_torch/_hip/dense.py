@@ -16,10 +16,7 @@ import torch
 
 from . import lib as L
 from . import streams as _streams
-
-
-def _r4(n):
-    return (int(n) + 3) // 4 * 4
+from .marshal import ptr, r4 as _r4
 
 
 class DenseSlab(object):
@@ -247,7 +244,6 @@ class DenseSlab(object):
         o.lr, o.eps, o.beta1, o.beta2 = float(lr), float(eps), float(beta1), float(beta2)
         if self.steps is None:
             self.steps = torch.zeros((1,), dtype=torch.int32, device=self.flat.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         L.check(L.lib().dctr_dense_opt_reg(ptr(self.flat), ptr(self.grad), ptr(self.state), ptr(self.state2),
                                            ptr(self.lam), self.numel, ctypes.byref(o), ptr(self.steps), stream),
                 "dctr_dense_opt_reg")

@@ -19,17 +19,10 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
+from .marshal import call, padded_rows, ptr, r4, rows2, rows3, workspace
 from ..layers.activation import Identity
 
 MAX_TOWER_WIDTH = 1152
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _r4(n):
-    return (int(n) + 3) // 4 * 4
 
 
 def tower_layers(dnn, dnn_linear=None):
@@ -64,18 +57,6 @@ def tower_layers(dnn, dnn_linear=None):
     return layers, w_out
 
 
-def _rows4(W):
-    """(tensor usable as a [N, K] weight with a 16-byte aligned base and ld % 4 == 0, ld).  A slab-seated
-    parameter (dense.DenseSlab) already is; anything else gets a zero-padded copy."""
-    if W.dim() == 2 and (W.shape[1] == 1 or W.stride(1) == 1) and W.stride(0) % 4 == 0 and W.stride(0) >= W.shape[1] \
-            and W.data_ptr() % 16 == 0:
-        return W, W.stride(0)
-    ld = _r4(W.shape[1])
-    buf = torch.zeros((W.shape[0], ld), dtype=torch.float32, device=W.device)
-    buf[:, :W.shape[1]].copy_(W.detach())
-    return buf, ld
-
-
 class _Meta(object):
     """Static description of one tower call (kept out of autograd's tensor arguments)."""
 
@@ -85,23 +66,24 @@ class _Meta(object):
         self.keep = bool(keep)           # a backward can follow (grad mode is off inside Function.forward)
 
 
-def _fill(desc, meta, Ws, lds, biases, hs, dhs, gWs, gbs, w_out, g_w_out):
-    desc.n_layers = len(Ws)
-    K = meta.K
-    for l, W in enumerate(Ws):
-        e = desc.layer[l]
-        e.W = W.data_ptr()
-        e.bias = biases[l].data_ptr() if biases[l] is not None else None
-        e.h = hs[l].data_ptr() if hs[l] is not None else None
-        e.dh = dhs[l].data_ptr() if dhs is not None else None
-        e.gW = gWs[l].data_ptr() if gWs is not None and gWs[l] is not None else None
-        e.gbias = gbs[l].data_ptr() if gbs is not None and gbs[l] is not None else None
-        e.K, e.N, e.ld_w = K, W.shape[0], lds[l]
-        e.ld_h = hs[l].stride(0) if hs[l] is not None else _r4(W.shape[0])
-        e.relu = meta.relus[l]
-        K = W.shape[0]
-    desc.w_out = w_out.data_ptr() if w_out is not None else None
-    desc.g_w_out = g_w_out.data_ptr() if g_w_out is not None else None
+def fill_desc(layers, w_out=None, g_w_out=None):
+    """A ``dctr_mlp_t`` over per-layer ``(W, bias, h, dh, gW, gbias, K, N, ld_w, ld_h, relu)`` (tensors or None, then ints)."""
+    desc = L.Mlp()
+    desc.n_layers = len(layers)
+    for e, (W, bias, h, dh, gW, gbias, K, N, ld_w, ld_h, relu) in zip(desc.layer, layers):
+        e.W, e.bias, e.h, e.dh, e.gW, e.gbias = ptr(W), ptr(bias), ptr(h), ptr(dh), ptr(gW), ptr(gbias)
+        e.K, e.N, e.ld_w, e.ld_h, e.relu = K, N, ld_w, ld_h, relu
+    desc.w_out, desc.g_w_out = ptr(w_out), ptr(g_w_out)
+    return desc
+
+
+def _tower_desc(meta, Ws, lds, biases, hs, dhs, gWs, gbs, w_out, g_w_out):
+    """The descriptor of a tower: layer l reads ``meta.K`` (l = 0) or layer l-1's outputs."""
+    Ks = [meta.K] + [W.shape[0] for W in Ws[:-1]]
+    at = lambda ts, l: ts[l] if ts is not None else None  # noqa: E731
+    return fill_desc([(W, biases[l], hs[l], at(dhs, l), at(gWs, l), at(gbs, l), Ks[l], W.shape[0], lds[l],
+                       hs[l].stride(0) if hs[l] is not None else r4(W.shape[0]), meta.relus[l])
+                      for l, W in enumerate(Ws)], w_out, g_w_out)
 
 
 class TowerFunction(torch.autograd.Function):
@@ -109,37 +91,30 @@ class TowerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        lib = L.lib()
         L.require_gpu(x, "DNN input")
         n = len(meta.relus)
         ctx.x_cols = x.shape[1]
         Wp = [params[2 * l] for l in range(n)]
         bp = [params[2 * l + 1] for l in range(n)]
         w_out = params[2 * n] if meta.has_out else None
-        if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16 \
-                or x.stride(0) < meta.K:
-            buf = torch.zeros((x.shape[0], _r4(meta.K)), dtype=torch.float32, device=x.device)
-            buf[:, :meta.K].copy_(x[:, :meta.K])
-            x = buf
+        x, _ = padded_rows(x, meta.K)
         B = x.shape[0]
         keep = meta.keep
         Ws, lds = [], []
         for W in Wp:
-            w, ld = _rows4(W)
+            w, ld = padded_rows(W)
             Ws.append(w)
             lds.append(ld)
         hs = []
         for l, W in enumerate(Wp):
             need = keep or (l == n - 1 and not meta.has_out)
-            hs.append(torch.empty((B, _r4(W.shape[0])), dtype=torch.float32, device=x.device) if need else None)
+            hs.append(torch.empty((B, r4(W.shape[0])), dtype=torch.float32, device=x.device) if need else None)
         logit = torch.empty((B,), dtype=torch.float32, device=x.device) if meta.has_out else None
         wo = w_out.reshape(-1) if w_out is not None else None
         if wo is not None and not wo.is_contiguous():
             wo = wo.contiguous()
-        desc = L.Mlp()
-        _fill(desc, meta, Ws, lds, bp, hs, None, None, None, wo, None)
-        L.check(lib.dctr_mlp_fwd(ctypes.byref(desc), _ptr(x), x.stride(0), B, _ptr(logit), L.stream_handle(x.device)),
-                "dctr_mlp_fwd")
+        desc = _tower_desc(meta, Ws, lds, bp, hs, None, None, None, wo, None)
+        call("dctr_mlp_fwd", ctypes.byref(desc), ptr(x), x.stride(0), B, ptr(logit), L.stream_handle(x.device))
         ctx.meta, ctx.n = meta, n
         ctx.lds = lds
         ctx.padded = [w is not W for w, W in zip(Ws, Wp)]
@@ -152,7 +127,6 @@ class TowerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.lib()
         meta, n = ctx.meta, ctx.n
         saved = ctx.saved_tensors
         x, wo = saved[0], saved[1]
@@ -167,8 +141,7 @@ class TowerFunction(torch.autograd.Function):
                 g = g.float().contiguous()
             ld_g = 0
         else:
-            if g.dtype != torch.float32 or g.stride(1) != 1:
-                g = g.float().contiguous()
+            g, _ = rows2(g, "DNN output gradient")
             ld_g = g.stride(0)
         sink = meta.sink
         dhs = [torch.empty_like(h) for h in hs]
@@ -197,12 +170,10 @@ class TowerFunction(torch.autograd.Function):
                 go_sink = go_sink.reshape(-1)
             g_wo = go_sink if go_sink is not None else torch.empty((wo.shape[0],), dtype=torch.float32, device=dev)
             rets.append(None if go_sink is not None else g_wo.reshape(1, -1))
-        desc = L.Mlp()
-        _fill(desc, meta, Ws, ctx.lds, bp, hs, dhs, gWs, gbs, wo, g_wo)
-        ws = torch.empty((max(1, lib.dctr_mlp_bwd_workspace_floats(ctypes.byref(desc), B)),), dtype=torch.float32,
-                         device=dev)
-        L.check(lib.dctr_mlp_bwd(ctypes.byref(desc), _ptr(x), x.stride(0), B, _ptr(g), ld_g, _ptr(gx),
-                                 gx.stride(0) if gx is not None else 0, _ptr(ws), L.stream_handle(dev)), "dctr_mlp_bwd")
+        desc = _tower_desc(meta, Ws, ctx.lds, bp, hs, dhs, gWs, gbs, wo, g_wo)
+        ws = workspace("dctr_mlp_bwd_workspace_floats", ctypes.byref(desc), B, device=dev)
+        call("dctr_mlp_bwd", ctypes.byref(desc), ptr(x), x.stride(0), B, ptr(g), ld_g, ptr(gx),
+             gx.stride(0) if gx is not None else 0, ptr(ws), L.stream_handle(dev))
         if gx is not None and gx.shape[1] != ctx.x_cols:
             gx = gx[:, :ctx.x_cols]
         return (gx, None) + tuple(rets)
@@ -272,14 +243,12 @@ def _act_backward(g, h, relu, want_bias):
     gb = None
     if g.is_cuda and g.dtype == torch.float32 and want_bias and g.dim() == 2 and \
             g.stride(1) == 1 and os.environ.get("DCTR_GLUE_KERNELS", "1") != "0":
-        lib = L.lib()
         B, N = g.shape
         go = torch.empty((B, N), dtype=torch.float32, device=g.device) if relu else None
         gb = torch.empty((N,), dtype=torch.float32, device=g.device)
-        ws = torch.empty((max(1, lib.dctr_relu_bwd_bias_workspace_floats(B, N)),), dtype=torch.float32, device=g.device)
-        L.check(lib.dctr_relu_bwd_bias(_ptr(g), g.stride(0), _ptr(h) if relu else None,
-                                       h.stride(0) if relu else 0, B, N, _ptr(go), N, _ptr(gb), _ptr(ws),
-                                       L.stream_handle(g.device)), "dctr_relu_bwd_bias")
+        ws = workspace("dctr_relu_bwd_bias_workspace_floats", B, N, device=g.device)
+        call("dctr_relu_bwd_bias", ptr(g), g.stride(0), ptr(h) if relu else None, h.stride(0) if relu else 0, B, N,
+             ptr(go), N, ptr(gb), ptr(ws), L.stream_handle(g.device))
         if relu:
             g = go
         elif not g.is_contiguous():
@@ -368,15 +337,14 @@ class BilinearWideFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, relu, E, V, dense, W0, b0, *weights):
         from . import ops as _ops
-        lib = L.lib()
-        E, lde = _ops._rows3(E, "Bilinear input")
-        V, ldv = _ops._rows3(V, "Bilinear second input")
+        E, lde = rows3(E, "Bilinear input")
+        V, ldv = rows3(V, "Bilinear second input")
         B, F, D = E.shape
         Wf = meta.flat_weights(weights)
         P = F * (F - 1) // 2
         n_dense = dense.shape[1] if dense is not None else 0
-        if dense is not None and (dense.stride(1) != 1 or dense.dtype != torch.float32):
-            dense = dense.float().contiguous()
+        if dense is not None:
+            dense, _ = rows2(dense, "Bilinear dense input")
         width = 2 * P * D + n_dense
         ld_out = _ops.slab_ld(width)
         # (whole tiles of 32 rows: the fused forward stores its pairs unconditionally)
@@ -388,19 +356,18 @@ class BilinearWideFunction(torch.autograd.Function):
             # pairs and first layer in one launch: the pairs feed the matrix cores from registers; x is a by-product
             # (the backward's weight-gradient GEMM reads it)
             h = torch.empty((B, W0.shape[0]), dtype=torch.float32, device=E.device)
-            ws = torch.empty((lib.dctr_bilinear_wide_fwd_workspace_floats(B, P),), dtype=torch.float32, device=E.device)
+            ws = workspace("dctr_bilinear_wide_fwd_workspace_floats", B, P, device=E.device)
             if any(ctx.needs_input_grad):
                 # W0 in the backward's operand layout, by the same packing launch
-                wpk_b = torch.empty((lib.dctr_bilinear_wide_pack_floats(P),), dtype=torch.float32, device=E.device)
-            L.check(lib.dctr_bilinear_wide_fwd(_ptr(E), lde, _ptr(V), ldv, _ptr(Wf), _ptr(sched[2]), P, F, D, B,
-                                               _ptr(dense), dense.stride(0) if dense is not None else 0, n_dense,
-                                               _ptr(W0), W0.stride(0), W0.shape[0], _ptr(b0), int(bool(relu)), _ptr(x),
-                                               ld_out, _ptr(h), h.stride(0), _ptr(ws), _ptr(wpk_b),
-                                               L.stream_handle(E.device)), "dctr_bilinear_wide_fwd")
+                wpk_b = workspace("dctr_bilinear_wide_pack_floats", P, device=E.device)
+            call("dctr_bilinear_wide_fwd", ptr(E), lde, ptr(V), ldv, ptr(Wf), ptr(sched[2]), P, F, D, B,
+                 ptr(dense), dense.stride(0) if dense is not None else 0, n_dense, ptr(W0), W0.stride(0), W0.shape[0],
+                 ptr(b0), int(bool(relu)), ptr(x), ld_out, ptr(h), h.stride(0), ptr(ws), ptr(wpk_b),
+                 L.stream_handle(E.device))
         else:
-            L.check(lib.dctr_bilinear_fwd(_ptr(E), lde, _ptr(V), ldv, _ptr(Wf), _ptr(sched[2]), sched[2].shape[0], P, F, D,
-                                          B, _ptr(x), ld_out, _ptr(dense), dense.stride(0) if dense is not None else 0,
-                                          n_dense, 2 * P * D, L.stream_handle(E.device)), "dctr_bilinear_fwd")
+            call("dctr_bilinear_fwd", ptr(E), lde, ptr(V), ldv, ptr(Wf), ptr(sched[2]), sched[2].shape[0], P, F, D,
+                 B, ptr(x), ld_out, ptr(dense), dense.stride(0) if dense is not None else 0, n_dense, 2 * P * D,
+                 L.stream_handle(E.device))
             h = torch.addmm(b0, x, W0.t()) if b0 is not None else torch.mm(x, W0.t())
             if relu:
                 h = torch.relu_(h)
@@ -410,18 +377,15 @@ class BilinearWideFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import ops as _ops
-        lib = L.lib()
         meta = ctx.meta
         E, V, Wf, x, W0, h, wpk_b = ctx.saved_tensors
-        E, lde = _ops._rows3(E, "Bilinear input")
-        V, ldv = _ops._rows3(V, "Bilinear second input")
+        E, lde = rows3(E, "Bilinear input")
+        V, ldv = rows3(V, "Bilinear second input")
         B, F, D = E.shape
         P = F * (F - 1) // 2
         dev = E.device
         g, gb = _act_backward(g, h, ctx.relu, ctx.has_bias and ctx.needs_input_grad[6])
-        if g.stride(1) != 1 or g.stride(0) % 4 != 0 or g.data_ptr() % 16 != 0:
-            g = g.contiguous()
+        g, _ = padded_rows(g)
         gW0 = None
         if ctx.needs_input_grad[5]:
             with _TunedGemm():
@@ -431,12 +395,11 @@ class BilinearWideFunction(torch.autograd.Function):
         gE = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         gV = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         gW = torch.empty((meta.n_w, D, D), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.dctr_bilinear_wide_bwd_workspace_floats(B, P),), dtype=torch.float32, device=dev)
+        ws = workspace("dctr_bilinear_wide_bwd_workspace_floats", B, P, device=dev)
         sched4, pair_w = meta.wide_tables(dev)
-        L.check(lib.dctr_bilinear_wide_bwd(_ptr(E), lde, _ptr(V), ldv, _ptr(Wf), _ptr(sched4), sched4.shape[0],
-                                           _ptr(pair_w), meta.n_w, P, F, D, B, _ptr(g), g.stride(0), _ptr(W0),
-                                           W0.stride(0), W0.shape[0], _ptr(gE), _ptr(gV), _ptr(gW), _ptr(ws),
-                                           _ptr(wpk_b), L.stream_handle(dev)), "dctr_bilinear_wide_bwd")
+        call("dctr_bilinear_wide_bwd", ptr(E), lde, ptr(V), ldv, ptr(Wf), ptr(sched4), sched4.shape[0],
+             ptr(pair_w), meta.n_w, P, F, D, B, ptr(g), g.stride(0), ptr(W0), W0.stride(0), W0.shape[0], ptr(gE),
+             ptr(gV), ptr(gW), ptr(ws), ptr(wpk_b), L.stream_handle(dev))
         return (None, None, gE, gV, None, gW0, gb) + tuple(gW[i] for i in range(ctx.n_w_in))
 
 
@@ -493,7 +456,6 @@ class TowerHeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, bias, meta, n_parts, *rest):
-        lib = L.lib()
         parts, params = list(rest[:n_parts]), rest[n_parts:]
         n = len(meta.relus)
         Wp = [params[2 * l] for l in range(n)]
@@ -502,18 +464,15 @@ class TowerHeadFunction(torch.autograd.Function):
         sink = meta.sink
         B, dev = x.shape[0], x.device
         ctx.x_cols = x.shape[1]
-        if x.dtype != torch.float32 or x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16 or x.stride(0) < meta.K:
-            buf = torch.zeros((B, _r4(meta.K)), dtype=torch.float32, device=dev)
-            buf[:, :meta.K].copy_(x[:, :meta.K])
-            x = buf
+        x, _ = padded_rows(x, meta.K)
         Ws, lds = [], []
         for W in Wp:
-            w, ld = _rows4(W)
+            w, ld = padded_rows(W)
             if w is not W:
                 raise RuntimeError("the fused train step needs slab-seated tower weights")
             Ws.append(w)
             lds.append(ld)
-        hs = [torch.empty((B, _r4(W.shape[0])), dtype=torch.float32, device=dev) for W in Wp]
+        hs = [torch.empty((B, r4(W.shape[0])), dtype=torch.float32, device=dev) for W in Wp]
         dhs = [torch.empty_like(h) for h in hs]
         gWs = [sink.grad_of(meta.param_refs[2 * l]) for l in range(n)]
         gbs = [sink.grad_of(meta.param_refs[2 * l + 1]) if bp[l] is not None else None for l in range(n)]
@@ -533,11 +492,9 @@ class TowerHeadFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         g_logit = torch.empty((B,), dtype=torch.float32, device=dev)
         gx = torch.empty((B, x.stride(0)), dtype=torch.float32, device=dev)
-        desc = L.Mlp()
-        _fill(desc, meta, Ws, lds, bp, hs, dhs, gWs, gbs, wo, g_wo)
-        ws = torch.empty((max(1, lib.dctr_mlp_train_workspace_floats(ctypes.byref(desc), B)),), dtype=torch.float32,
-                         device=dev)
-        pp = [_ptr(p) for p in ps] + [None] * (2 - len(ps))
+        desc = _tower_desc(meta, Ws, lds, bp, hs, dhs, gWs, gbs, wo, g_wo)
+        ws = workspace("dctr_mlp_train_workspace_floats", ctypes.byref(desc), B, device=dev)
+        pp = [ptr(p) for p in ps] + [None] * (2 - len(ps))
         # The weight gradients need only what the first launch leaves behind (x, h, dh, g_logit) and nothing but the
         # dense optimizer needs THEM: with a fork stream on the sink they run beside the embedding update (which needs
         # only gx / g_logit) instead of in front of it.  The sink joins the fork before the dense optimizer step.
@@ -546,10 +503,9 @@ class TowerHeadFunction(torch.autograd.Function):
             sink.join()       # a previous step's forked weight-gradient / optimizer kernels wrote the weights read below
         fork = sink.fork_stream(dev) if (hasattr(sink, "fork_stream") and inline is None) else None
         defer = fork is None and inline is None and getattr(sink, "overlap", False) == "defer" and x.device.type == "cuda"
-        L.check(lib.dctr_mlp_train_step(ctypes.byref(desc), _ptr(x), x.stride(0), B, pp[0], pp[1], _ptr(bias), _ptr(y),
-                                        _ptr(y_pred), _ptr(loss), _ptr(g_logit), _ptr(g_bias), _ptr(gx), gx.stride(0),
-                                        _ptr(ws), 1 if (fork is not None or defer or inline is not None) else 0, None,
-                                        L.stream_handle(dev)), "dctr_mlp_train_step")
+        call("dctr_mlp_train_step", ctypes.byref(desc), ptr(x), x.stride(0), B, pp[0], pp[1], ptr(bias), ptr(y),
+             ptr(y_pred), ptr(loss), ptr(g_logit), ptr(g_bias), ptr(gx), gx.stride(0), ptr(ws),
+             1 if (fork is not None or defer or inline is not None) else 0, None, L.stream_handle(dev))
         if inline is not None:
             # In-kernel optimizer: the weight gradients and their reduction follow in line on THIS stream and step the
             # parameters as they finish; the embedding update (which needs only gx / g_logit) is what leaves for the
@@ -559,25 +515,22 @@ class TowerHeadFunction(torch.autograd.Function):
             upd = getattr(sink, "update_stream", None)
             if upd is not None:
                 upd.wait_stream(torch.cuda.current_stream(dev))      # the update may start once this launch is done
-            L.check(lib.dctr_mlp_train_wgrad(ctypes.byref(desc), _ptr(x), x.stride(0), B, _ptr(g_logit), _ptr(ws),
-                                             _ptr(loss), _ptr(g_bias), ctypes.byref(inline), L.stream_handle(dev)),
-                    "dctr_mlp_train_wgrad")
+            call("dctr_mlp_train_wgrad", ctypes.byref(desc), ptr(x), x.stride(0), B, ptr(g_logit), ptr(ws),
+                 ptr(loss), ptr(g_bias), ctypes.byref(inline), L.stream_handle(dev))
             sink.inline_done = True
         if defer:
             keep = (x, hs, dhs, ws, g_logit, loss, ps, y, wo, gx, desc)
 
             def launch(stream, keep=keep, B=B, g_bias=g_bias):
                 x_, ws_, g_logit_, loss_, desc_ = keep[0], keep[3], keep[4], keep[5], keep[10]
-                L.check(lib.dctr_mlp_train_wgrad(ctypes.byref(desc_), _ptr(x_), x_.stride(0), B, _ptr(g_logit_),
-                                                 _ptr(ws_), _ptr(loss_), _ptr(g_bias), None,
-                                                 ctypes.c_void_p(stream.cuda_stream)), "dctr_mlp_train_wgrad")
+                call("dctr_mlp_train_wgrad", ctypes.byref(desc_), ptr(x_), x_.stride(0), B, ptr(g_logit_), ptr(ws_),
+                     ptr(loss_), ptr(g_bias), None, ctypes.c_void_p(stream.cuda_stream))
             sink.deferred = launch
         if fork is not None:
             side = fork
             side.wait_stream(torch.cuda.current_stream(dev))     # fork point: right behind the tower kernel
-            L.check(lib.dctr_mlp_train_wgrad(ctypes.byref(desc), _ptr(x), x.stride(0), B, _ptr(g_logit), _ptr(ws),
-                                             _ptr(loss), _ptr(g_bias), None, ctypes.c_void_p(side.cuda_stream)),
-                    "dctr_mlp_train_wgrad")
+            call("dctr_mlp_train_wgrad", ctypes.byref(desc), ptr(x), x.stride(0), B, ptr(g_logit), ptr(ws),
+                 ptr(loss), ptr(g_bias), None, ctypes.c_void_p(side.cuda_stream))
             # everything the forked kernels touch stays allocated until the join (no record_stream bookkeeping)
             sink.forked(side, (x, hs, dhs, ws, g_logit, loss, ps, y, wo))
         ctx.shapes = [tuple(p.shape) for p in parts]
@@ -625,7 +578,6 @@ class BCEHeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, bias, unit, g_bias_sink, *parts):
-        lib = L.lib()
         ps = []
         for p in parts:
             L.require_gpu(p, "logit part")
@@ -644,9 +596,9 @@ class BCEHeadFunction(torch.autograd.Function):
         g_logit = torch.empty((B,), dtype=torch.float32, device=dev)
         g_bias = g_bias_sink if g_bias_sink is not None else (
             torch.empty((1,), dtype=torch.float32, device=dev) if bias is not None else None)
-        pp = [_ptr(p) for p in ps] + [None] * (4 - len(ps))
-        L.check(lib.dctr_bce_head(pp[0], pp[1], pp[2], pp[3], _ptr(bias), _ptr(y), B, _ptr(y_pred), _ptr(loss),
-                                  _ptr(g_logit), _ptr(g_bias), L.stream_handle(dev)), "dctr_bce_head")
+        pp = [ptr(p) for p in ps] + [None] * (4 - len(ps))
+        call("dctr_bce_head", pp[0], pp[1], pp[2], pp[3], ptr(bias), ptr(y), B, ptr(y_pred), ptr(loss),
+             ptr(g_logit), ptr(g_bias), L.stream_handle(dev))
         ctx.unit, ctx.sunk = bool(unit), g_bias_sink is not None
         ctx.shapes = [tuple(p.shape) for p in parts]
         ctx.save_for_backward(g_logit, g_bias if (bias is not None and g_bias_sink is None) else None)

@@ -633,7 +633,7 @@ class EmbeddingPlan(object):
         self.__dict__.setdefault("unpooled_columns", ())
         self._reset_device_image()
 
-    # ---- sparse-update mode (see ops.py) ---------------------------------------------------------
+    # ---- sparse-update mode (see ops/embed.py) ---------------------------------------------------------
     @property
     def update(self):
         return self._owner.update if self._owner is not None else self._update

@@ -33,14 +33,7 @@ import torch
 from . import lib as L
 from . import mlp as _mlp
 from . import streams as _streams
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _r4(n):
-    return (int(n) + 3) // 4 * 4
+from .marshal import padded_rows, ptr as _ptr, r4 as _r4
 
 
 class _Buffers(object):
@@ -102,7 +95,7 @@ class GatherStep(object):
         f32 = dict(dtype=torch.float32, device=dev)
         Ws, lds, bp = [], [], []
         for (W, bias, _) in self.layers:
-            w, ld = _mlp._rows4(W)
+            w, ld = padded_rows(W)
             if w is not W:          # (not slab-seated: the autograd route copes with it)
                 self._bufs[key] = False
                 return None
@@ -115,8 +108,7 @@ class GatherStep(object):
         gbs = [slab.grad_of(bias) if bias is not None else None for (_, bias, _) in self.layers]
         g_wo = slab.grad_of(self.w_out).reshape(-1)
         meta = _mlp._Meta([r for (_, _, r) in self.layers], True, plan.width)
-        b.desc = L.Mlp()
-        _mlp._fill(b.desc, meta, Ws, lds, bp, b.hs, b.dhs, gWs, gbs, self.w_out.reshape(-1), g_wo)
+        b.desc = _mlp._tower_desc(meta, Ws, lds, bp, b.hs, b.dhs, gWs, gbs, self.w_out.reshape(-1), g_wo)
         ok = plan.unit_path and plan.update_kernel_ok(B) and \
             lib.dctr_embed_tower_train_supported(ctypes.byref(plan.cplan), ctypes.byref(b.desc), int(B)) == 1
         if not ok:

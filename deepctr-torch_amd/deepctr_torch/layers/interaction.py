@@ -236,7 +236,7 @@ class CIN(nn.Module):
             self.activation._forward_hooks or self.activation._forward_pre_hooks))
 
     def _stack(self, x, F, D, w_head):
-        """The whole stack as one autograd node (_hip/ops.py CINStackFunction): ``x`` the ``[B, F, D]`` field matrix or a
+        """The whole stack as one autograd node (_hip/ops/cin.py CINStackFunction): ``x`` the ``[B, F, D]`` field matrix or a
         ``[B, >= F*D]`` row matrix that starts with it; ``w_head``: None, or the ``[1, featuremap_num]`` weight of the
         bias-free projection a model puts on the output (xDeepFM's cin_linear) -- the result is then ``[B, 1]``."""
         wb = []

@@ -50,7 +50,7 @@ class xDeepFM(BaseModel):
             if not hooked and self.cin._stack_ok(nf) and type(self.cin_linear) is nn.Linear:
                 # CIN + cin_linear as one autograd node on the gather's row matrix itself: the gradient comes back in
                 # that shape, the projection is a wave-per-row dot product forward and folded into the layers'
-                # gradient assembly backward (_hip/ops.py CINStackFunction)
+                # gradient assembly backward (_hip/ops/cin.py CINStackFunction)
                 parts.append(self.cin._stack(dnn_input, nf, plan.emb_dim, self.cin_linear.weight))
             else:
                 cin_input = dnn_input[:, :plan.emb_width].reshape(B, nf, plan.emb_dim)   # view of the gather's output

@@ -2,7 +2,7 @@
 
 * ``dctr_iafm_fwd / _bwd``: the forward restates the formula include/dctr.h documents, in torch on the caller's host
   buffers; the backward is torch.autograd of that forward (as tests/mock_ops.py does) -- an independent check of the
-  marshalling in deepctr_torch/_hip/ops.py, not a second copy of the kernel's hand-derived gradients;
+  marshalling in deepctr_torch/_hip/ops/fm.py, not a second copy of the kernel's hand-derived gradients;
 * ``dctr_embed_fwd / _update / _bwd`` for plans with DCTR_PLAN_WIDE_PER_FIELD: the deep side is left to the stand-in's own
   entry points (called without a wide buffer), the wide side is served per field here.  Plans without the bit go to the
   originals untouched.

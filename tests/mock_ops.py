@@ -2,7 +2,7 @@
 
 Each forward restates the formula include/dctr.h documents for the entry point, with torch on the caller's host
 buffers; each backward is torch.autograd of that forward -- no hand-derived gradients here, so these stand-ins are an
-independent check of the argument marshalling in deepctr_torch/_hip/ops.py, not a second copy of the kernels' math."""
+independent check of the argument marshalling in deepctr_torch/_hip/ops/ and _hip/marshal.py, not a second copy of the kernels' math."""
 import itertools
 
 import numpy as np
