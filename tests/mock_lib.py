@@ -628,8 +628,35 @@ class _Core(object):
         else:
             w -= f(o.lr) * g
 
-    def _lazy_pass(self, mode, units, n_units, ids_t, n, step, optref, sweep_k=0):
+    # (the places where a row is chosen are methods of their own: tests/test_lazy_abi_host.py replaces them one at a time
+    # to show that the C-ABI cases notice)
+    @staticmethod
+    def _sweep_rows(t, sweep_k, vocab):
+        """dctr_lazy_sweep: the (t mod K)-th of K windows of a table's rows"""
+        wlen = (vocab + sweep_k - 1) // sweep_k
+        return np.arange(min((t % sweep_k) * wlen, vocab), min((t % sweep_k + 1) * wlen, vocab))
+
+    @staticmethod
+    def _batch_rows(ids, vocab):
+        """every row of the batch once; ids outside [0, vocab) mean row 0"""
+        return np.unique(np.where((ids < 0) | (ids >= vocab), 0, ids).astype(np.int64))
+
+    @staticmethod
+    def _lazy_refusal(units, n_units, step, optref, vec, max_dim):
+        """include/dctr.h / csrc/lazy.hip check(): the code of a call that must not touch anything, or 0"""
+        if not units or n_units <= 0 or not step or optref is None:
+            return -1
+        if optref._obj.kind not in (0, 1, 2, 3) or vec not in (1, 4):
+            return -1
+        if max_dim < 1 or max_dim > 64 * vec:
+            return -2
+        return 0
+
+    def _lazy_pass(self, mode, units, n_units, ids_t, n, step, optref, sweep_k=0, vec=4, max_dim=1):
         from deepctr_torch._hip import lib as L
+        rc = self._lazy_refusal(units, n_units, step, optref, vec, max_dim)
+        if rc or n <= 0:
+            return rc
         o = optref._obj
         t = int(_arr(step, (1,), dtype=np.int32)[0])
         target = t + 1 if mode == 1 else t
@@ -638,13 +665,12 @@ class _Core(object):
         for u in range(n_units):
             un = arr[u]
             stamp = _arr(un.stamp, (un.vocab,), dtype=np.int32)
-            if mode == 2 and sweep_k > 0:       # dctr_lazy_sweep: the (t mod K)-th of K windows of this table's rows
-                wlen = (un.vocab + sweep_k - 1) // sweep_k
-                rows = np.arange((t % sweep_k) * wlen, min((t % sweep_k + 1) * wlen, un.vocab))
+            if mode == 2 and sweep_k > 0:
+                rows = self._sweep_rows(t, sweep_k, un.vocab)
             elif mode == 2:
                 rows = np.arange(min(n, un.vocab))
             else:
-                rows = np.unique(np.where((ids[u] < 0) | (ids[u] >= un.vocab), 0, ids[u]).astype(np.int64))
+                rows = self._batch_rows(ids[u], un.vocab)
             rows = rows[stamp[rows] < target]
             if not len(rows):
                 continue
@@ -682,29 +708,63 @@ class _Core(object):
                     Bv[rows] = b
         return 0
 
+    def _lazy_order(self, units, n_units, ids_t, B, step, optref, order_ws):
+        """order_ws (include/dctr.h): with B >= 64 and steps to replay, every unit's entries dealt by how long their rows
+        slept, longest first -- a permutation of 0 .. B-1 per unit; otherwise the scratch is left alone"""
+        from deepctr_torch._hip import lib as L
+        o = optref._obj
+        if not order_ws or B < 64 or B > (1 << 18) or (o.kind in (0, 1) and not o.any_l2):
+            return
+        t = int(_arr(step, (1,), dtype=np.int32)[0])
+        arr = (L.LazyUnit * n_units).from_address(units.value)
+        ids = _arr(ids_t, (n_units * B,), dtype=np.int32).reshape(n_units, B)
+        out = _arr(order_ws, (n_units * B,), dtype=np.int32).reshape(n_units, B)
+        for u in range(n_units):
+            rows = np.where((ids[u] < 0) | (ids[u] >= arr[u].vocab), 0, ids[u]).astype(np.int64)
+            gap = np.maximum(t - _arr(arr[u].stamp, (arr[u].vocab,), dtype=np.int32)[rows], 0)
+            out[u] = np.argsort(-gap, kind="stable")
+
     def dctr_lazy_catchup(self, units, n_units, ids_t, B, step, opt, vec, max_dim, order_ws, stream):
         self.calls.append("lazy_catchup")
-        return self._lazy_pass(0, units, n_units, ids_t, B, step, opt)
+        if B < 0 or (B > 0 and not ids_t):
+            return -1
+        if B > 0 and not self._lazy_refusal(units, n_units, step, opt, vec, max_dim):
+            self._lazy_order(units, n_units, ids_t, B, step, opt, order_ws)
+        return self._lazy_pass(0, units, n_units, ids_t, B, step, opt, vec=vec, max_dim=max_dim)
 
     def dctr_lazy_apply(self, units, n_units, ids_t, B, step, opt, vec, max_dim, stream):
         self.calls.append("lazy_apply")
-        return self._lazy_pass(1, units, n_units, ids_t, B, step, opt)
+        if B < 0 or (B > 0 and not ids_t):
+            return -1
+        return self._lazy_pass(1, units, n_units, ids_t, B, step, opt, vec=vec, max_dim=max_dim)
 
     def dctr_lazy_flush(self, units, n_units, max_vocab, step, opt, vec, max_dim, stream):
         self.calls.append("lazy_flush")
-        return self._lazy_pass(2, units, n_units, None, max_vocab, step, opt)
+        if max_vocab < 0:
+            return -1
+        return self._lazy_pass(2, units, n_units, None, max_vocab, step, opt, vec=vec, max_dim=max_dim)
 
     def dctr_lazy_sweep(self, units, n_units, max_vocab, K, step, opt, vec, max_dim, stream):
         self.calls.append("lazy_sweep")
-        return self._lazy_pass(2, units, n_units, None, max_vocab, step, opt, sweep_k=int(K))
+        if max_vocab < 0 or K <= 0:
+            return -1
+        return self._lazy_pass(2, units, n_units, None, max_vocab, step, opt, sweep_k=int(K), vec=vec, max_dim=max_dim)
 
     def dctr_lazy_step_inc(self, step, stream):
+        if not step:
+            return -1
         _arr(step, (1,), dtype=np.int32)[0] += 1
         return 0
 
     def dctr_dense_opt_reg(self, p, g, s1, s2, lam, n, optref, step, stream):
         self.calls.append("dense_opt_reg")
+        if not p or not g or n < 0 or optref is None or not step:
+            return -1
         o = optref._obj
+        if o.kind not in (0, 1, 2, 3) or (o.kind in (1, 3) and not s1) or (o.kind == 2 and not (s1 and s2)):
+            return -1
+        if n == 0:
+            return 0
         T = int(_arr(step, (1,), dtype=np.int32)[0]) + 1
         P, G = _arr(p, (n,)), _arr(g, (n,))
         A = _arr(s1, (n,)) if _arr(s1, (1,)) is not None else np.zeros(n, np.float32)
