@@ -32,6 +32,7 @@
 // -- the compiler specialises it before it is inlined; those kernels then get other machine code than they have beside
 // callers with other multiples.  tools/isa_diff.py compares the listings.)
 #include "tower_tiles.hpp"
+#include "wgrad_assign.hpp"
 
 namespace {
 
@@ -1164,10 +1165,18 @@ __global__ __launch_bounds__(kTW, 2) void k_mlp_wgrad(WgradArgs A) {
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int blk = blockIdx.x;
   MLP_TRACE(A.trace, 0);
-  int l = 0;
-  while (l < A.n_layers && blk >= A.blk0[l + 1]) ++l;
-  const int local = blk - A.blk0[l];
-  const int s = local % A.S;
+  // GEMM workgroups: (slice, tile) by the XCD-local list of wgrad_assign.hpp; `local` is the pair's place in the plain
+  // order (tile * S + slice within its layer), which is what names its partial.  Projection workgroups keep their ids.
+  const int n_gemm = A.blk0[A.n_layers];
+  int l = A.n_layers, local = blk - n_gemm, s = 0;
+  if (blk < n_gemm) {
+    const int n_tiles = n_gemm / A.S;
+    const int e = wgrad_assign(blk, n_gemm);
+    s = e / n_tiles;
+    int t = e - s * n_tiles;
+    for (l = 0; l + 1 < A.n_layers && t >= (A.blk0[l + 1] - A.blk0[l]) / A.S; ++l) t -= (A.blk0[l + 1] - A.blk0[l]) / A.S;
+    local = t * A.S + s;
+  }
   const int rb0 = s * A.bs;
   const int rb1 = (rb0 + A.bs < A.B) ? rb0 + A.bs : A.B;
   float* part = A.part + static_cast<int64_t>(s) * A.slab;

@@ -368,22 +368,140 @@ __global__ __launch_bounds__(kSortT) void k_prepass_sort(UpdArgs A) {
 }
 
 // ---- X -> ids_t (+ parts_t) (standalone; the forward kernel fuses the same thing) -------------------
+// Warming.  This kernel is the first of the step to hold the NEXT batch's ids, and in the step engine it runs a tower's
+// length ahead of that batch's gather, behind the previous update on its queue.  The gather's second round trip is a
+// chip-wide burst of random rows from tables far larger than any cache; a row requested here is in the
+// memory-side cache when the gather asks.  So the thread that holds an id issues one load per 64-byte piece of the rows
+// the gather will read -- the gather's own address expressions -- and throws the values away.  A load cannot change what
+// a later load returns: results are the same with or without it.  An id outside the vocabulary issues nothing (the gather
+// reads row 0 for it and raises the plan's error word; neither is touched here).
+//   WarmSide: the address terms of one table as a unit reads it (vocab 0: no table, or nothing is warmed -- no id is
+//   inside it).  warm_first: the row's first piece, one plain load whose value the caller keeps alive up to the END of
+//   the kernel (a use of the value is where the wave would wait for it).  warm_rest: the pieces behind the first, of rows
+//   longer than 64 bytes or not aligned to them, folded into `rest` (the fold waits: call it when every first piece is
+//   under way).  Both kernels below warm through these.
+struct WarmSide {
+  const float* table;
+  int64_t vocab, ld;
+  int32_t dim, pad_;
+};
+// field i's terms as the descriptor has them (i < 0 or !on: none); warm_only: what is left of them for warming
+__device__ __forceinline__ WarmSide warm_side(const dctr_field_t* __restrict__ f, int i, bool on) {
+  WarmSide s = {nullptr, 0, 0, 0, 0};
+  if (on && i >= 0) {
+    s.table = f[i].table; s.vocab = f[i].vocab; s.ld = row_ld(f[i]); s.dim = f[i].dim;
+  }
+  return s;
+}
+__device__ __forceinline__ WarmSide warm_only(WarmSide s, bool warm) {
+  if (!warm || !s.table) s.vocab = 0;
+  return s;
+}
+__device__ __forceinline__ bool id_in_vocab(int32_t id, int64_t vocab) {
+  return static_cast<uint64_t>(static_cast<int64_t>(id)) < static_cast<uint64_t>(vocab);
+}
+__device__ __forceinline__ void warm_first(const WarmSide& s, int32_t id, float& first) {
+  if (id_in_vocab(id, s.vocab)) first = ldg_f32(s.table + id * s.ld);
+}
+__device__ __forceinline__ void warm_rest(const WarmSide& s, int32_t id, uint32_t& rest) {
+  if (!id_in_vocab(id, s.vocab)) return;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(s.table + id * s.ld), a1 = a0 + 4u * static_cast<uintptr_t>(s.dim);
+#pragma unroll 4
+  for (uintptr_t a = (a0 | 63) + 1; a < a1; a += 64)
+    rest ^= __builtin_bit_cast(uint32_t, ldg_f32(reinterpret_cast<const float*>(a)));
+}
+
+// A workgroup takes kIdsRows samples and every unit, kIdsUnits units per pass.  Reading, a thread's items run along a
+// sample's row of X (a unit's id columns are neighbours: the tile's lines are fetched once, by this workgroup -- one thread
+// per (unit, sample) in unit-major order read X with a stride of a row, and a line was fetched by as many workgroups as
+// there are units); the ids turn through LDS and leave along b, as ids_t / parts_t are laid out.
+constexpr int kIdsRows = 16, kIdsUnits = 64;
+constexpr int kIdsPer = kIdsRows * kIdsUnits / kThreads;
+static_assert(kIdsRows * kIdsUnits % kThreads == 0, "whole items per thread");
+constexpr int64_t kWarmBytes = int64_t(64) << 20;   // a quarter of the 256 MiB memory-side cache (dctr_embed_ids)
 __global__ __launch_bounds__(kThreads) void k_embed_ids(const dctr_field_t* __restrict__ deep,
                                                         const dctr_field_t* __restrict__ wide,
                                                         const int32_t* __restrict__ units, int n_units,
                                                         const float* __restrict__ X, int64_t ldx, int B,
                                                         int32_t* __restrict__ ids_t, uint16_t* __restrict__ parts_t,
-                                                        int n_parts) {
+                                                        int n_parts, int warm) {
   step_priority();
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-  if (i >= static_cast<int64_t>(n_units) * B) return;
-  const int u = static_cast<int>(i / B), b = static_cast<int>(i - static_cast<int64_t>(u) * B);
-  const int32_t id = static_cast<int32_t>(X[static_cast<int64_t>(b) * ldx + units[4 * u + 2]]);
-  ids_t[i] = id;
-  if (parts_t) {
-    const int di = units[4 * u], wi = units[4 * u + 1];
-    const int64_t vocab = (di >= 0) ? deep[di].vocab : wide[wi].vocab;
-    parts_t[i] = static_cast<uint16_t>(static_cast<uint32_t>(clamp_id(id, vocab)) % static_cast<uint32_t>(n_parts));
+  // ids on their way from X's order to ids_t's (rows of kIdsRows + 1 words: the writes run down a column, and a stride of 16
+  // would put a wave's 64 writes into four banks)
+  constexpr int kSidLd = kIdsRows + 1;
+  __shared__ int32_t sid[kIdsUnits * kSidLd];
+  // the pass's units: the vocabulary the partition tag clamps to, and the two tables to warm
+  __shared__ int64_t s_pv[kIdsUnits];
+  __shared__ WarmSide s_deep[kIdsUnits], s_wide[kIdsUnits];
+  const int tid = threadIdx.x;
+  const int b0 = static_cast<int>(blockIdx.x) * kIdsRows;
+  const int nb = (B - b0 < kIdsRows) ? B - b0 : kIdsRows;
+  for (int u0 = 0; u0 < n_units; u0 += kIdsUnits) {
+    const int nu = (n_units - u0 < kIdsUnits) ? n_units - u0 : kIdsUnits;
+    const int n_it = nb * nu;
+    // two chains of loads side by side: id column -> X (every thread's items; an item past the end repeats item 0, so that
+    // no load sits behind a branch and all are under way at once), and unit -> field descriptors -> LDS (thread = unit)
+    int col[kIdsPer];
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) {
+      const int j = tid + q * kThreads < n_it ? tid + q * kThreads : 0;
+      col[q] = ldg_i32(units + 4 * (u0 + j % nu) + 2);
+    }
+    int di = -1, wi = -1;
+    if (tid < nu) {
+      di = ldg_i32(units + 4 * (u0 + tid));
+      wi = ldg_i32(units + 4 * (u0 + tid) + 1);
+    }
+    int32_t id[kIdsPer];
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) {
+      const int j = tid + q * kThreads < n_it ? tid + q * kThreads : 0;
+      id[q] = static_cast<int32_t>(ldg_f32(X + static_cast<int64_t>(b0 + j / nu) * ldx + col[q]));
+    }
+    const WarmSide sd = warm_side(deep, di, warm || parts_t), sw = warm_side(wide, wi, warm || parts_t);
+    if (tid < nu) {
+      s_pv[tid] = (di >= 0) ? sd.vocab : sw.vocab;
+      s_deep[tid] = warm_only(sd, warm);
+      s_wide[tid] = warm_only(sw, warm);
+    }
+    __syncthreads();
+    float kd[kIdsPer], kw[kIdsPer];
+    uint32_t rest = 0;
+    // every row's first piece leaves before anything waits for one
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) {
+      const int j = tid + q * kThreads;
+      kd[q] = kw[q] = 0.f;
+      if (j < n_it) {
+        warm_first(s_deep[j % nu], id[q], kd[q]);
+        warm_first(s_wide[j % nu], id[q], kw[q]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) {
+      const int j = tid + q * kThreads;
+      if (j < n_it) warm_rest(s_deep[j % nu], id[q], rest);    // (a wide value is one float: no piece behind the first)
+    }
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) {
+      const int j = tid + q * kThreads;
+      const int bl = j / nu, uu = j - bl * nu;
+      if (j < n_it) sid[uu * kSidLd + bl] = id[q];
+    }
+    __syncthreads();
+    for (int j = tid; j < n_it; j += kThreads) {
+      const int uu = j / nb, bl = j - uu * nb;
+      const int32_t v = sid[uu * kSidLd + bl];
+      const int64_t i = static_cast<int64_t>(u0 + uu) * B + b0 + bl;
+      ids_t[i] = v;
+      if (parts_t)
+        parts_t[i] = static_cast<uint16_t>(static_cast<uint32_t>(clamp_id(v, s_pv[uu])) % static_cast<uint32_t>(n_parts));
+    }
+    __syncthreads();
+    // (the warming loads' only use: here, behind the pass's stores)
+#pragma unroll
+    for (int q = 0; q < kIdsPer; ++q) asm volatile("" ::"v"(kd[q]), "v"(kw[q]));
+    asm volatile("" ::"v"(rest));
   }
 }
 
@@ -397,18 +515,30 @@ __global__ __launch_bounds__(kThreads) void k_embed_ids_gen(const dctr_field_t* 
                                                             const dctr_vunit_t* __restrict__ vunits, int n_vcols,
                                                             const float* __restrict__ X, int64_t ldx, int B,
                                                             int32_t* __restrict__ ids_t, uint16_t* __restrict__ parts_t,
-                                                            float* __restrict__ den_t, UpdArgs A) {
+                                                            float* __restrict__ den_t, UpdArgs A, int warm) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (i >= static_cast<int64_t>(n_vcols) * B) return;
   const int c = static_cast<int>(i / B), b = static_cast<int>(i - static_cast<int64_t>(c) * B);
   const dctr_uslot_t s = slots[c];
   const float* xr = X + static_cast<int64_t>(b) * ldx;
   const int32_t rid = static_cast<int32_t>(xr[s.col]);
-  ids_t[i] = rid;
   const bool by_len = s.len_col >= 0;
   const int32_t len_i = by_len ? static_cast<int32_t>(xr[s.len_col]) : 0;
   bool valid = true;
   if (s.pool == DCTR_POOL_SUM || s.pool == DCTR_POOL_MEAN) valid = by_len ? (s.t < len_i) : (rid != 0);
+  // warming as in k_embed_ids, for the positions that are entries: the row of the unit's deep table where this column
+  // feeds a deep field (goff >= 0) and the wide value where it carries one -- the columns of a shared table differ in that
+  float kd = 0.f, kw = 0.f;
+  uint32_t rest = 0;
+  if (warm && valid) {
+    const dctr_vunit_t* d = vunits + s.vu0;
+    const WarmSide sd = warm_only(warm_side(deep, d->di, s.goff >= 0), true);
+    const WarmSide sw = warm_only(warm_side(wide, d->wi, s.wide != 0), true);
+    warm_first(sd, rid, kd);
+    warm_first(sw, rid, kw);
+    warm_rest(sd, rid, rest);
+  }
+  ids_t[i] = rid;
   if (den_t && s.den >= 0 && s.t == 0) {
     float cnt = 0.f;
     if (by_len) {
@@ -431,6 +561,7 @@ __global__ __launch_bounds__(kThreads) void k_embed_ids_gen(const dctr_field_t* 
     }
     parts_t[i] = static_cast<uint16_t>(tag);
   }
+  asm volatile("" ::"v"(kd), "v"(kw), "v"(rest));
 }
 
 // Partitions per unit: ~3/4 of a tile per workgroup (a partition's size is Poisson-like: mean 96 of 128 leaves
@@ -507,6 +638,13 @@ extern "C" int dctr_embed_ids(const dctr_plan_t* plan, const int32_t* units, int
   if (B == 0) return DCTR_OK;
   const int n_parts = parts_t ? dctr_embed_update_partitions(plan, B) : 0;
   if (parts_t && (n_parts <= 0 || n_parts > 65535)) return DCTR_ENOSUP;
+  // warm the rows the gather will read (k_embed_ids): only with a plan (its tables), and only while the lines touched, 128
+  // bytes per row of every (column, sample) and table side, stay under a quarter of the memory-side cache -- a launch that
+  // saturates the cache evicts what it warms
+  const int64_t cols = (plan && plan->ext) ? plan->ext->n_vcols : n_units;
+  const int sides = plan ? (plan->n_deep > 0 ? 1 : 0) + (plan->n_wide > 0 ? 1 : 0) : 0;
+  const bool tables = plan && (plan->n_deep <= 0 || plan->deep) && (plan->n_wide <= 0 || plan->wide);
+  const int warm = (tables && sides > 0 && cols * B * sides * 128 <= kWarmBytes) ? 1 : 0;
   if (plan && plan->ext) {      // general units: ids_t / parts_t are [n_vcols, B]; den_t rides along
     const dctr_plan_ext_t* x = plan->ext;
     if (n_units != x->n_vunits || !x->slots || !x->vunits || x->n_vcols <= 0) return DCTR_EINVAL;
@@ -516,13 +654,12 @@ extern "C" int dctr_embed_ids(const dctr_plan_t* plan, const int32_t* units, int
     const int64_t n = static_cast<int64_t>(x->n_vcols) * B;
     k_embed_ids_gen<<<dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                       static_cast<hipStream_t>(stream)>>>(plan->deep, plan->wide, x->slots, x->vunits, x->n_vcols, X, ldx, B,
-                                                          ids_t, parts_t, x->den_t, a);
+                                                          ids_t, parts_t, x->den_t, a, warm);
     return launch_status();
   }
-  const int64_t n = static_cast<int64_t>(n_units) * B;
-  k_embed_ids<<<dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+  k_embed_ids<<<dim3(static_cast<unsigned>((B + kIdsRows - 1) / kIdsRows)), dim3(kThreads), 0,
                 static_cast<hipStream_t>(stream)>>>(plan ? plan->deep : nullptr, plan ? plan->wide : nullptr, units,
-                                                    n_units, X, ldx, B, ids_t, parts_t, n_parts);
+                                                    n_units, X, ldx, B, ids_t, parts_t, n_parts, warm);
   return launch_status();
 }
 
