@@ -304,6 +304,15 @@ __device__ __forceinline__ void stage_slots(const UpdArgs& A, const UnitCtx& U, 
   for (int i = tid; i < n; i += nthreads) dst[i] = *(const DCTR_GLOBAL uint32_t*)(src + i);
 }
 
+// The multiply-adds of the update, fused BY HAND.  `a * b + c` left to the compiler is contracted at one inlined copy of
+// apply_strip and not at another (VEC = 2, Adagrad: v_pk_fma in the general kernel's single-tile path, v_pk_mul + v_add in
+// the pre-sorted kernel's tiles), and the routes through the update -- scan, buckets, pre-sorted -- then differ by an ulp
+// where include/dctr.h promises the same bits.  What goes through here: apply_strip's SGD and Adagrad steps, the FM terms
+// g_fm * S and - (sum g_fm) * e of simple and general entries, and wdense_column's g_wide * X (inlined into both kernels).
+// Not lazy_apply_strip (csrc/lazy_opt.hpp writes its own fused operations; DCTR_UPD_LAZY has one route) and not
+// dense_step_apply (common.hpp: contraction off).
+__device__ __forceinline__ float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
 // One optimizer step on a strip of a row.  OPT: 0 SGD, 1 Adagrad, 2 accumulate into gacc.
 // off_w / off_s / off_g: float offsets of the strip in the table, the state slab and the (contiguous) gacc slab.
 template <int VEC, int OPT>
@@ -314,14 +323,14 @@ __device__ __forceinline__ void apply_strip(const dctr_field_t& fd, int64_t off_
   if (OPT == DCTR_UPD_ADAGRAD) {  // torch.optim.Adagrad: s += g*g ; p -= lr * g / (sqrt(s) + eps)
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
-      ns.v[i] = s.v[i] + G.v[i] * G.v[i];
-      nw.v[i] = w.v[i] - lr * (G.v[i] / (sqrtf(ns.v[i]) + eps));
+      ns.v[i] = fused(G.v[i], G.v[i], s.v[i]);
+      nw.v[i] = fused(-lr, G.v[i] / (sqrtf(ns.v[i]) + eps), w.v[i]);
     }
     strip_store<VEC>(fd.state + off_s, ns);
     strip_store<VEC>(fd.table + off_w, nw);
   } else if (OPT == DCTR_UPD_SGD) {  // torch.optim.SGD: p -= lr * g
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) nw.v[i] = w.v[i] - lr * G.v[i];
+    for (int i = 0; i < VEC; ++i) nw.v[i] = fused(-lr, G.v[i], w.v[i]);
     strip_store<VEC>(fd.table + off_w, nw);
   } else {  // dense-gradient semantics: gacc[row] += g   (w holds the gacc strip)
 #pragma unroll
@@ -340,8 +349,8 @@ __device__ __forceinline__ void wdense_column(const UpdArgs& A, int j) {
   float acc = 0.f;
 #pragma unroll 8
   for (int b = tid; b < A.B; b += kThreads)
-    acc += ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw + A.gwd_col) *
-           ldg_f32(A.X + static_cast<int64_t>(b) * A.ldx + col);
+    acc = fused(ldg_f32(A.gwide + static_cast<int64_t>(b) * A.ldgw + A.gwd_col),
+                ldg_f32(A.X + static_cast<int64_t>(b) * A.ldx + col), acc);
   acc = wave_sum(acc);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
@@ -390,11 +399,11 @@ __device__ __forceinline__ void gen_entry(const UpdArgs& A, const EntryDesc& E, 
   if (deep) {
     if (E.pool == DCTR_POOL_NONE) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) h.v[k] += gfl * S.v[k];      // (- g_fm e is folded at the row: e IS the table row)
+      for (int k = 0; k < VEC; ++k) h.v[k] = fused(gfl, S.v[k], h.v[k]);   // (- g_fm e is folded at the row: e IS the table row)
       gf = gfl;
     } else {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) h.v[k] += gfl * (S.v[k] - pv.v[k]);
+      for (int k = 0; k < VEC; ++k) h.v[k] = fused(gfl, S.v[k] - pv.v[k], h.v[k]);
       if (E.pool == DCTR_POOL_MEAN) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) h.v[k] = h.v[k] / den;
@@ -523,7 +532,7 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
         const Strip<VEC> S = strip_load<VEC>(A.fm_s + static_cast<int64_t>(b) * A.lds_ + e0);
         gf = ldg_f32(A.gfm + b);
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) h.v[k] += gf * S.v[k];
+        for (int k = 0; k < VEC; ++k) h.v[k] = fused(gf, S.v[k], h.v[k]);
       }
     }
     if (wide_on && gl == 0) gw = ldg_f32(gwbase + static_cast<int64_t>(b) * A.ldgw);
@@ -571,7 +580,7 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
       if (lane_on) {
         if (fold) {
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) acc.v[k] -= accf * e.v[k];
+          for (int k = 0; k < VEC; ++k) acc.v[k] = fused(-accf, e.v[k], acc.v[k]);
         }
         const Strip<VEC> b2 = Z.s2 ? strip_load<VEC>(Z.s2 + row * Z.dim + e0) : strip_zero<VEC>();
         lazy_apply_strip<VEC>(A, Z, Z.lam2d, Z.deep + row * Z.ld_d + e0, Z.s1 ? Z.s1 + row * Z.ld_s1 + e0 : nullptr,
@@ -592,7 +601,7 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
     if (lane_on) {
       if (fold) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc.v[k] -= accf * e.v[k];
+        for (int k = 0; k < VEC; ++k) acc.v[k] = fused(-accf, e.v[k], acc.v[k]);
       }
       apply_strip<VEC, OPT>(fd, row * ld_dw + e0, row * ld_ds + e0, row * fd.dim + e0, acc, w, s, A.lr, A.eps);
     }
@@ -1192,7 +1201,7 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
     }
     if (lane_on) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) gbuf[grp * RW + e0 + k] = GEN ? h.v[k] : h.v[k] + gf * S.v[k];   // (gf = 0, S = 0 without FM)
+      for (int k = 0; k < VEC; ++k) gbuf[grp * RW + e0 + k] = GEN ? h.v[k] : fused(gf, S.v[k], h.v[k]);   // (gf = 0, S = 0 without FM)
     }
     if (gl == 0) {
       gfbuf[grp] = gf;
@@ -1221,7 +1230,7 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
             Strip<VEC> a2 = acc;
             if (fold) {
 #pragma unroll
-              for (int k = 0; k < VEC; ++k) a2.v[k] -= accf * e.v[k];
+              for (int k = 0; k < VEC; ++k) a2.v[k] = fused(-accf, e.v[k], a2.v[k]);
             }
             lazy_apply_strip<VEC>(A, Z, Z.lam2d, Z.deep + row * Z.ld_d + e0, Z.s1 ? Z.s1 + row * Z.ld_s1 + e0 : nullptr,
                                   Z.s2 ? Z.s2 + row * Z.dim + e0 : nullptr, a2, w, s, s2);
@@ -1241,7 +1250,7 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
           Strip<VEC> a2 = acc;
           if (fold) {
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) a2.v[k] -= accf * e.v[k];
+            for (int k = 0; k < VEC; ++k) a2.v[k] = fused(-accf, e.v[k], a2.v[k]);
           }
           apply_strip<VEC, OPT>(fd, row * ld_dw + e0, row * ld_ds + e0, row * fd.dim + e0, a2, w, s, A.lr, A.eps);
         }

@@ -176,7 +176,8 @@ size_t dctr_sizeof_plan(void);
  * sequence.py:49-77), Linear.forward (basemodel.py:63-92), FM.forward (interaction.py:26-34) and
  * combined_dnn_input (inputs.py:126-138).
  *   X     [B, ldx]   the model input matrix (ids as float32)
- *   out   [B, ld_out] row b = [ deep field slices at field.out_off | dense block at plan.dense_off ]
+ *   out   [B, ld_out] row b = [ deep field slices at field.out_off | dense block at plan.dense_off ]; only those are
+ *         written: the padding of a row (and of a wide / fm_s row) keeps what the caller left there
  *   wide  [B]  sum_f w_f[id] (+pooled VarLen) + dense . Linear.weight     (nullable); element b lives at
  *         wide[b * ld_wide] (ld_wide = 1 for a plain vector; a column of `out` for the sharded exchange)
  *   fm    [B]  0.5 * sum_d ((sum_f e)^2 - sum_f e^2) over ALL deep fields (nullable; needs emb_dim)
@@ -240,7 +241,9 @@ int dctr_embed_apply(const dctr_plan_t* plan, const float* X, int64_t ldx, int32
  *          g_wide[b] lives at g_wide[b * ld_gw]
  *   opt    DCTR_UPD_SGD      table[row] -= lr * G                          (torch.optim.SGD)
  *          DCTR_UPD_ADAGRAD  state[row] += G*G ; table[row] -= lr*G/(sqrt(state[row])+eps)
- *          DCTR_UPD_ACCUM    gacc[row]  += G          (exact dense-gradient semantics: param.grad)
+ *          DCTR_UPD_ACCUM    gacc[row]  += G          (exact dense-gradient semantics: param.grad; a second launch
+ *                            onto a non-zero gacc adds to it)
+ *          Rows whose id is not in the batch are not written, in any of the three modes.
  *   max_vocab  largest vocab over the plan's fields (sizes the 32-bit sort keys)
  *   g_wdense [plan.n_wdense] (nullable): when given, n_wdense extra workgroups also write the gradient of the dense
  *          half of Linear, g_wdense[j] = sum_b g_wide[b] * X[b, wdense_cols[j]] (basemodel.py:86-90), in a
@@ -299,9 +302,10 @@ int dctr_embed_segments(const dctr_plan_t* plan, const int32_t* units, int32_t n
                         const int32_t* ids_t, const uint16_t* parts_t, int32_t B, int32_t* workspace,
                         int64_t workspace_ints, dctr_stream_t stream);
 /* workspace (nullable): dctr_embed_update_workspace_ints(plan, n_units, B) int32, ZERO before the first use (the
- * kernels leave it ready for the next launch).  With it (and presorted = 0) a pre-pass buckets the (unit, sample)
- * entries by partition, so no workgroup scans a unit's B ids: worth it for large (global) batches; without it every
- * workgroup scans.  presorted = 1: see dctr_embed_segments.                                                     */
+ * kernels leave it ready for the next launch: its first n_units * P counters are zero again once dctr_embed_update's
+ * launch has run, nothing behind the advertised size is touched).  With it (and presorted = 0) a pre-pass buckets
+ * the (unit, sample) entries by partition, so no workgroup scans a unit's B ids: worth it for large (global)
+ * batches; without it every workgroup scans.  presorted = 1: see dctr_embed_segments.                          */
 int64_t dctr_embed_update_workspace_ints(const dctr_plan_t* plan, int32_t n_units, int32_t B);
 
 /* ---- FM on an explicit [B, F, D] tensor (interaction.py:26-34) ------------------------------------

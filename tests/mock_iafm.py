@@ -42,7 +42,7 @@ def extend(mock):
     orig_fwd, orig_update, orig_bwd = mock.dctr_embed_fwd, mock.dctr_embed_update, mock.dctr_embed_bwd
 
     def per_field(pref):
-        return bool(pref._obj.flags & WIDE_PER_FIELD)
+        return pref is not None and bool(pref._obj.flags & WIDE_PER_FIELD)
 
     # ---- the kernel pair -------------------------------------------------------------------------------------------
     def dctr_iafm_supported(F, D):
@@ -86,11 +86,12 @@ def extend(mock):
         if not per_field(pref):
             return orig_fwd(pref, X, ldx, B, out, ld_out, wide, ld_wide, fm, err, units, n_units, ids_t, parts_t, fm_s,
                             ld_s, stream)
+        if not _null(wide) and ld_wide < pref._obj.n_wide + 1:
+            return -1          # (DCTR_EINVAL, include/dctr.h)
         rc = orig_fwd(pref, X, ldx, B, out, ld_out, None, 1, fm, err, units, n_units, ids_t, parts_t, fm_s, ld_s, stream)
-        if rc or _null(wide):
+        if rc or _null(wide) or B == 0:
             return rc
         c, deep, widef, dcols, wcols = mock._plan(pref)
-        assert ld_wide >= c.n_wide + 1
         Xv = _arr(X, (B, c.n_xcols), ldx)
         W = _arr(wide, (B, c.n_wide + 1), ld_wide)
         for f, fd in enumerate(widef):

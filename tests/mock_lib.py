@@ -26,6 +26,14 @@ def _arr(ptr, shape, ld=None, dtype=np.float32):
     return np.lib.stride_tricks.as_strided(flat, shape=(rows, cols), strides=(ld * 4, 4))
 
 
+def _nul(p):
+    """a NULL pointer argument (None, 0 or an empty c_void_p)"""
+    if p is None:
+        return True
+    v = p.value if isinstance(p, ctypes.c_void_p) else p
+    return not v if isinstance(v, (int, type(None))) else False
+
+
 def _tab(f):
     """the table of a field descriptor, honouring its row stride (dctr_field_t.ld; 0 = contiguous)"""
     return _arr(f.table, (f.vocab, f.dim), f.ld or f.dim)
@@ -253,13 +261,58 @@ class _Core(object):
         x = L.PlanExt.from_address(c.ext)
         return x, (L.USlot * x.n_vcols).from_address(x.slots), (L.VUnit * x.n_vunits).from_address(x.vunits)
 
+    # (the places where the contract decides something are methods of their own: tests/test_embed_abi_host.py replaces them
+    # one at a time to show that the C-ABI cases of tests/embed_abi.py notice)
     @staticmethod
-    def _rows(X, f, err=None):
-        ids = X[:, f.col].astype(np.int64)
+    def _trunc_ids(col):
+        """Tensor.long() of a column of X: truncation toward zero"""
+        return col.astype(np.int32)
+
+    @staticmethod
+    def _entry_valid(valid):
+        """which positions of a sum / mean pooled slot are entries of the update (the others carry the tag 0xFFFF)"""
+        return valid
+
+    @staticmethod
+    def _argmax(v):
+        """max pooling over [B, len, dim]: the position of the FIRST maximum per element"""
+        return v.argmax(axis=1)
+
+    @staticmethod
+    def _clamp_rows(ids, vocab):
+        """an id outside [0, vocab) means row 0"""
+        ids = np.asarray(ids, np.int64)
+        return np.where((ids < 0) | (ids >= vocab), 0, ids)
+
+    def _rows(self, X, f, err=None):
+        ids = self._trunc_ids(X[:, f.col]).astype(np.int64)
         bad = (ids < 0) | (ids >= f.vocab)
         if err is not None and bad.any():
-            err[0] = 1
-        return np.where(bad, 0, ids)
+            err[0] |= 1
+        return self._clamp_rows(ids, f.vocab)
+
+    # ---- what include/dctr.h's entry points check before they launch (csrc/embed_tile.hpp check_plan, csrc/update.hip) -----
+    @staticmethod
+    def _check_plan(pref, X, ldx, B):
+        if pref is None or _nul(X) or B < 0:
+            return -1
+        c = pref._obj
+        if c.n_xcols <= 0 or ldx < c.n_xcols or c.n_deep < 0 or c.n_wide < 0 or c.n_deep_fixed > c.n_deep or \
+                c.n_wide_fixed > c.n_wide or (c.n_deep and not c.deep) or (c.n_wide and not c.wide) or c.vec not in (1, 2, 4):
+            return -1
+        return -2 if c.max_dim > 64 * c.vec else 0
+
+    @staticmethod
+    def _lane_layout(c):
+        """(floats per lane, lanes per row) of the sorted update: a tile is 256 / lanes entries"""
+        vec = c.vec if c.n_deep > 0 else 1
+        if vec == 4 and c.emb_dim > 0 and c.emb_dim % 8 == 0 and c.emb_dim <= 64:
+            vec = 8
+        need = (c.max_dim + vec - 1) // vec if c.n_deep > 0 else 1
+        lpr = 1
+        while lpr < need:
+            lpr <<= 1
+        return vec, lpr
 
     @staticmethod
     def _seq(X, f, err=None):
@@ -308,23 +361,57 @@ class _Core(object):
         return ids.reshape(-1), g.reshape(-1, f.dim)
 
     def dctr_embed_update_supported(self, pref, max_vocab, B):
-        return 1
+        """include/dctr.h: the plan / batch fit (B <= 2^20, keys fit 32 bits)"""
+        if pref is None or B <= 0:
+            return 0
+        c = pref._obj
+        if c.vec not in (1, 2, 4) or (c.n_deep > 0 and c.max_dim > 64 * c.vec) or B > (1 << 20) or max_vocab >= (1 << 31):
+            return 0
+        if c.ext:
+            return 1
+        if c.n_deep != c.n_deep_fixed or c.n_wide != c.n_wide_fixed:
+            return 0
+        P = max(1, (int(B) + 191) // 192)
+        return int((max(int(max_vocab), 1) // P + 1).bit_length() + max(int(B) - 1, 1).bit_length() <= 32)
 
     def dctr_embed_update_workspace_ints(self, pref, n_units, B):
-        return 4
+        """a counter and 512 keys per (unit, partition) bucket"""
+        if pref is None or n_units <= 0 or B <= 0:
+            return 0
+        ext = self._ext(pref)
+        return (ext[0].n_vunits if ext is not None else int(n_units)) * self.dctr_embed_update_partitions(pref, B) * 513
 
     def dctr_embed_segments(self, pref, units, n_units, max_vocab, ids_t, parts_t, B, ws, ws_n, stream):
-        """(the pre-pass only re-orders work inside the device code: nothing to compute for the stand-in)"""
+        """(the pre-pass only re-orders work inside the device code: nothing to compute for the stand-in -- the argument
+        checks are the header's)"""
         self.calls.append("embed_segments")
+        if pref is None or _nul(units) or _nul(ids_t) or _nul(ws) or n_units <= 0 or B < 0:
+            return -1
+        if B == 0:
+            return 0
+        if not self.dctr_embed_update_supported(pref, max_vocab, B):
+            return -2
+        ext = self._ext(pref)
+        if ext is not None and (n_units != ext[0].n_vunits or _nul(parts_t)):
+            return -1
+        if ws_n < int(n_units) * self.dctr_embed_update_partitions(pref, B) * 513:
+            return -1
         return 0
 
     def dctr_embed_update_partitions(self, pref, B):
-        return max(1, (int(B) + 95) // 96)
+        """partitions per unit: a partition holds about 3/4 of a tile of 256 / lanes-per-row entries"""
+        if pref is None or B <= 0:
+            return 0
+        per = max(1, (256 // self._lane_layout(pref._obj)[1]) * 3 // 4)
+        return max(1, (int(B) + per - 1) // per)
 
     def dctr_embed_ids(self, pref, units, n_units, X, ldx, B, ids_t, parts_t, stream):
-        """(parts_t -- the update kernel's partition tags -- is an optimisation detail of the device code: the
-        stand-in's update does not read it, and leaves it unwritten)"""
+        """ids_t [n_units, B] and, given a plan, parts_t = clamp(id) mod dctr_embed_update_partitions"""
         self.calls.append("embed_ids")
+        if _nul(units) or _nul(X) or _nul(ids_t) or n_units <= 0 or B < 0 or (not _nul(parts_t) and pref is None):
+            return -1
+        if B == 0:
+            return 0
         ext = self._ext(pref)
         if ext is not None:
             # general units: ids_t / parts_t are [n_vcols, B]; a masked-out position carries the tag 0xFFFF (every other
@@ -344,7 +431,12 @@ class _Core(object):
                 if sl.pool in (1, 2):
                     valid = (sl.t < Xv[:, sl.len_col].astype(np.int32)) if sl.len_col >= 0 else (rid != 0)
                 if tags is not None:
-                    tags[ci] = np.where(valid, 0, 0xFFFF).astype(np.uint16)
+                    # a valid entry's tag: its partition of the unit, clamp(id) mod (k P); a masked-out position: 0xFFFF
+                    vu = ext[2][sl.vu0]
+                    _, deep, widef, _, _ = self._plan(pref)
+                    vocab = deep[vu.di].vocab if vu.di >= 0 else widef[vu.wi].vocab
+                    kP = vu.k * self.dctr_embed_update_partitions(pref, B)
+                    tags[ci] = np.where(self._entry_valid(valid), self._clamp_rows(rid, vocab) % kP, 0xFFFF).astype(np.uint16)
                 if den is not None and sl.den >= 0 and sl.t == 0:
                     cnt = Xv[:, sl.len_col].astype(np.int32).astype(np.float32) if sl.len_col >= 0 else \
                         (Xv[:, sl.col:sl.col + sl.len].astype(np.int32) != 0).sum(axis=1).astype(np.float32)
@@ -355,33 +447,58 @@ class _Core(object):
         Xv = _arr(X, (B, ncol), ldx)
         out = _arr(ids_t, (n_units * B,), dtype=np.int32).reshape(n_units, B)
         for u in range(n_units):
-            out[u] = Xv[:, U[u, 2]].astype(np.int32)
+            out[u] = self._trunc_ids(Xv[:, U[u, 2]])
+        if not _nul(parts_t):
+            c, deep, widef, _, _ = self._plan(pref)
+            P = self.dctr_embed_update_partitions(pref, B)
+            if P <= 0 or P > 65535:
+                return -2
+            tags = _arr(parts_t, (n_units * B,), dtype=np.uint16).reshape(n_units, B)
+            for u in range(n_units):
+                vocab = deep[U[u, 0]].vocab if U[u, 0] >= 0 else widef[U[u, 1]].vocab
+                tags[u] = self._clamp_rows(out[u], vocab) % P
         return 0
 
     def dctr_embed_fwd(self, pref, X, ldx, B, out, ld_out, wide, ld_wide, fm, err, units, n_units, ids_t, parts_t,
                        fm_s, ld_s, stream):
         self.calls.append("embed_fwd")
+        rc = self._check_plan(pref, X, ldx, B)
+        if rc:
+            return rc
         c, deep, widef, dcols, wcols = self._plan(pref)
+        if not _nul(wide) and (ld_wide < 1 or ((c.flags & 8) and ld_wide < c.n_wide + 1)):
+            return -1
+        if B == 0:
+            return 0
+        if (not _nul(fm) and (c.emb_dim <= 0 or _nul(out))) or \
+                (not _nul(fm_s) and (c.emb_dim <= 0 or _nul(out) or ld_s < c.emb_dim)) or \
+                (not _nul(ids_t) and (_nul(units) or n_units <= 0)) or (not _nul(parts_t) and _nul(ids_t)) or \
+                (c.ext and not _nul(ids_t)):
+            return -1
+        if c.vec > 1:
+            for p, ld in ((fm_s, ld_s), (out, ld_out)):
+                if not _nul(p) and (ld % c.vec or (p.value if isinstance(p, ctypes.c_void_p) else int(p)) % (4 * c.vec)):
+                    return -3
         Xv = _arr(X, (B, c.n_xcols), ldx)
         errv = _arr(err, (1,), dtype=np.int32)
         S = np.zeros((B, max(c.emb_dim, 1)), np.float32)
         Q = np.zeros_like(S)
         if out is not None and _arr(out, (1,)) is not None:
+            # (only the field slices and the dense block are written: the padding of a row is the caller's)
             O = _arr(out, (B, ld_out), ld_out)
-            O[...] = 0
             for f in deep:
                 e = self._gather(Xv, f, errv)
                 O[:, f.out_off:f.out_off + f.dim] = e
                 if c.emb_dim > 0:
                     S += e
                     Q += e * e
-            for j, col in enumerate(dcols):
+            for j, col in enumerate(dcols if c.dense_off >= 0 else []):          # (dense_off = -1: no dense block)
                 O[:, c.dense_off + j] = Xv[:, col]
         if _arr(wide, (1,)) is not None:
             w = np.zeros(B, np.float32)
             for f in widef:
                 w += self._gather(Xv, f, errv)[:, 0]
-            if wcols:
+            if wcols and c.wdense_w:          # (wdense_w = NULL: no dense half)
                 ww = _arr(c.wdense_w, (len(wcols),))
                 for j, col in enumerate(wcols):
                     w += Xv[:, col] * ww[j]
@@ -389,9 +506,7 @@ class _Core(object):
         if _arr(fm, (1,)) is not None:
             _arr(fm, (B,))[...] = 0.5 * np.sum(S * S - Q, axis=1)
         if _arr(fm_s, (1,)) is not None:
-            Sv = _arr(fm_s, (B, ld_s), ld_s)
-            Sv[...] = 0
-            Sv[:, :c.emb_dim] = S[:, :c.emb_dim]
+            _arr(fm_s, (B, c.emb_dim), ld_s)[...] = S[:, :c.emb_dim]
         if _arr(ids_t, (1,)) is not None:
             self.dctr_embed_ids(pref, units, n_units, X, ldx, B, ids_t, parts_t, stream)
             self.calls.pop()
@@ -406,14 +521,25 @@ class _Core(object):
                     if f.pool == 3 and offs[i] >= 0:
                         ids, mask = self._seq(Xv, f)
                         m = mask[:, :, None].astype(np.float32)
-                        arg = (_tab(f)[ids] - (np.float32(1) - m) * np.float32(1e9)).argmax(axis=1)      # first maximum
+                        arg = self._argmax(_tab(f)[ids] - (np.float32(1) - m) * np.float32(1e9))
                         A[:, offs[i]:offs[i] + f.dim] = arg.astype(np.uint8)
         return 0
 
     # ---- general backward (dctr_embed_bwd) + consume pass (dctr_embed_apply): pooled fields, shared tables -----
     def dctr_embed_bwd(self, pref, X, ldx, B, g_out, ld_g, out, ld_out, g_fm, g_wide, mode, lr, stream):
         self.calls.append("embed_bwd:%d" % mode)
+        rc = self._check_plan(pref, X, ldx, B)
+        if rc or B == 0:
+            return rc
         c, deep, widef, dcols, wcols = self._plan(pref)
+        if mode not in (0, 1) or (mode == 0 and not c.flags & 1) or (not _nul(g_fm) and (_nul(out) or c.emb_dim <= 0)):
+            return -1
+        if mode == 1 and c.flags & 4:
+            return -2
+        if c.vec > 1:
+            for on, p, ld in ((g_out, g_out, ld_g), (g_fm, out, ld_out)):
+                if not _nul(on) and (ld % c.vec or (p.value if isinstance(p, ctypes.c_void_p) else int(p)) % (4 * c.vec)):
+                    return -3
         Xv = _arr(X, (B, c.n_xcols), ldx)
         gO = _arr(g_out, (B, ld_g), ld_g) if ld_g else None
         gF, gW = _arr(g_fm, (B,)), _arr(g_wide, (B,))
@@ -437,7 +563,12 @@ class _Core(object):
 
     def dctr_embed_apply(self, pref, X, ldx, B, opt, lr, eps, stream):
         self.calls.append("embed_apply:%d" % opt)
+        rc = self._check_plan(pref, X, ldx, B)
+        if rc or B == 0:
+            return rc
         c, deep, widef, dcols, wcols = self._plan(pref)
+        if not c.flags & 1 or opt not in (0, 1) or (opt == 1 and not c.flags & 2):
+            return -1
         Xv = _arr(X, (B, c.n_xcols), ldx)
         for f in deep + widef:
             rows = np.unique(self._seq(Xv, f)[0])
@@ -458,9 +589,79 @@ class _Core(object):
     def dctr_embed_update_lazy(self, *a):
         return -2          # (DCTR_ENOSUP: the stand-in keeps the two-pass route)
 
+    # (simple units: one method per decision of the contract, see ``_trunc_ids``)
+    @staticmethod
+    def _segment_sums(rows, G):
+        """(touched rows, the sum of every row's duplicates, added one at a time in sample order)"""
+        order = np.argsort(rows, kind="stable")
+        r, Gs = rows[order], G[order]
+        uniq, start, cnt = np.unique(r, return_index=True, return_counts=True)
+        acc = np.zeros((len(uniq), G.shape[1]), np.float32)
+        for k in range(int(cnt.max()) if len(cnt) else 0):
+            on = cnt > k
+            acc[on] += Gs[start[on] + k]
+        return uniq, acc
+
+    @staticmethod
+    def _state_increment(uniq, acc, rows, G):
+        """Adagrad: the square of the row's summed gradient"""
+        return acc * acc
+
+    @staticmethod
+    def _fm_term(gF, S, e):
+        """FM's backward for a fixed field: g_fm (S - e), e the row before the step"""
+        return gF[:, None] * (S - e)
+
+    @staticmethod
+    def _accumulate(gacc, uniq, acc):
+        gacc[uniq] += acc
+
+    @staticmethod
+    def _unit_sides(di, wi):
+        """the tables a unit feeds (either may be -1)"""
+        return di, wi
+
+    def _update_refusal(self, pref, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, fm_s, ld_s, g_fm, g_wide,
+                        ld_gw, opt, X, g_wdense, ws, ws_n, presorted):
+        """csrc/update.hip, embed_update_impl: the code of a call that must not touch anything, or 0"""
+        if opt == 3 or pref is None or _nul(units) or _nul(ids_t) or n_units <= 0 or B < 0:
+            return -1
+        c = pref._obj
+        ext = self._ext(pref)
+        if ext is not None:
+            x = ext[0]
+            if n_units != x.n_vunits or _nul(parts_t) or not x.slots or not x.vunits or (not _nul(g_fm) and _nul(out)) or \
+                    (x.n_den > 0 and not x.den_t) or (x.ld_amax > 0 and not x.amax):
+                return -1
+        if not _nul(g_wide) and (ld_gw < 1 or ((c.flags & 8) and ld_gw < c.n_wide + 1)):
+            return -1
+        if not _nul(g_wdense) and (_nul(X) or _nul(g_wide) or c.n_wdense <= 0 or not c.wdense_cols):
+            return -1
+        if B == 0:
+            return 0
+        if opt not in (0, 1, 2):
+            return -1
+        if not self.dctr_embed_update_supported(pref, max_vocab, B):
+            return -2
+        if (opt == 2 and not c.flags & 1) or (opt == 1 and not c.flags & 2) or \
+                (not _nul(g_fm) and (_nul(fm_s) or c.emb_dim <= 0)):
+            return -1
+        if c.n_deep > 0 and c.vec > 1:
+            for on, p, ld in ((g_out, g_out, ld_g), (g_fm, fm_s, ld_s)):
+                if not _nul(on) and (ld % c.vec or (p.value if isinstance(p, ctypes.c_void_p) else int(p)) % (4 * c.vec)):
+                    return -3
+        if presorted and (_nul(ws) or ws_n < (ext[0].n_vunits if ext is not None else int(n_units)) *
+                          self.dctr_embed_update_partitions(pref, B) * 513):
+            return -1
+        return 0
+
     def dctr_embed_update(self, pref, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, ld_out, fm_s, ld_s, g_fm,
                           g_wide, ld_gw, opt, lr, eps, X, ld_x, g_wdense, wd_step, ws, ws_n, presorted, stream):
         self.calls.append("embed_update:%d" % opt)
+        rc = self._update_refusal(pref, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, fm_s, ld_s, g_fm, g_wide,
+                                  ld_gw, opt, X, g_wdense, ws, ws_n, presorted)
+        if rc or B == 0:
+            return rc
         c, deep, widef, dcols, wcols = self._plan(pref)
         gO = _arr(g_out, (B, ld_g), ld_g) if ld_g else None
         gF = _arr(g_fm, (B,))
@@ -479,35 +680,33 @@ class _Core(object):
         def scatter(f, rows, G):
             """sum duplicates in sample order, then one read-modify-write per touched row."""
             table = _tab(f)
-            uniq, inv = np.unique(rows, return_inverse=True)
-            acc = np.zeros((len(uniq), f.dim), np.float32)
-            for b in range(B):
-                acc[inv[b]] += G[b]
+            uniq, acc = self._segment_sums(rows, G)
             if opt == 0:
                 table[uniq] -= np.float32(lr) * acc
             elif opt == 1:
                 st = _st(f)
-                st[uniq] += acc * acc
+                st[uniq] += self._state_increment(uniq, acc, rows, G)
                 table[uniq] -= np.float32(lr) * (acc / (np.sqrt(st[uniq]) + np.float32(eps)))
             else:
-                _arr(f.gacc, (f.vocab, f.dim))[uniq] += acc
+                self._accumulate(_arr(f.gacc, (f.vocab, f.dim)), uniq, acc)
 
+        work = []          # (every gradient from the tables as they stand: FM's e is the row BEFORE the step)
         for u in range(n_units):
-            di, wi = int(U[u, 0]), int(U[u, 1])
-            if di >= 0:
+            di, wi = self._unit_sides(int(U[u, 0]), int(U[u, 1]))
+            if di >= 0 and (gO is not None or gF is not None):
                 f = deep[di]
-                rows = np.where((ids[u] < 0) | (ids[u] >= f.vocab), 0, ids[u]).astype(np.int64)
+                rows = self._clamp_rows(ids[u], f.vocab)
                 G = np.zeros((B, f.dim), np.float32)
                 if gO is not None:
                     G += gO[:, f.out_off:f.out_off + f.dim]
                 if gF is not None:
-                    e = _arr(out, (B, ld_out), ld_out)[:, f.out_off:f.out_off + f.dim]
-                    G += gF[:, None] * (_arr(fm_s, (B, ld_s), ld_s)[:, :f.dim] - e)
-                scatter(f, rows, G)
+                    G += self._fm_term(gF, _arr(fm_s, (B, f.dim), ld_s), _tab(f)[rows])
+                work.append((f, rows, G))
             if wi >= 0 and gW is not None:
                 f = widef[wi]
-                rows = np.where((ids[u] < 0) | (ids[u] >= f.vocab), 0, ids[u]).astype(np.int64)
-                scatter(f, rows, gW.reshape(B, 1).astype(np.float32))
+                work.append((f, self._clamp_rows(ids[u], f.vocab), gW.reshape(B, 1).astype(np.float32)))
+        for f, rows, G in work:
+            scatter(f, rows, G)
         if _arr(g_wdense, (1,)) is not None and gW is not None and wcols:
             Xv = _arr(X, (B, c.n_xcols), ld_x)
             _arr(g_wdense, (len(wcols),))[...] = [np.dot(gW.astype(np.float64), Xv[:, col]) for col in wcols]
