@@ -87,38 +87,10 @@ __global__ __launch_bounds__(kThreads) void k_embed_segments(UpdArgs A) {
     if (tid == 0) n_sh = 0;
     __syncthreads();
     // phase 1: the samples whose partition tag is mine (no dependent loads inside the divergent branches)
-    auto keep = [&](int b) {
+    scan_tags(pt, B, (A.B & 7) == 0, pp, [&](int b) {
       const int slot = atomicAdd(&n_sh, 1);
       if (slot < kBucket) keys[slot] = static_cast<uint32_t>(b);
-    };
-    if ((A.B & 7) == 0) {
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      const DCTR_GLOBAL u32x4* pv = (const DCTR_GLOBAL u32x4*)pt;
-      const int nvec = B >> 3;
-      for (int c0 = 0; c0 < nvec; c0 += 2 * kThreads) {
-        u32x4 v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int idx = c0 + q * kThreads + tid;
-          v[q] = pv[idx < nvec ? idx : 0];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int idx = c0 + q * kThreads + tid;
-          if (idx < nvec) {
-            const uint32_t d[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if ((d[j] & 0xFFFFu) == pp) keep(8 * idx + 2 * j);
-              if ((d[j] >> 16) == pp) keep(8 * idx + 2 * j + 1);
-            }
-          }
-        }
-      }
-    } else {
-      for (int b = tid; b < B; b += kThreads)
-        if (static_cast<uint32_t>(*(const DCTR_GLOBAL uint16_t*)(pt + b)) == pp) keep(b);
-    }
+    });
     __syncthreads();
     n = n_sh;
     if (tid == 0) *(DCTR_GLOBAL int32_t*)cnt = n;
@@ -830,46 +802,6 @@ int embed_update_impl(const dctr_plan_t* plan, const int32_t* units, int32_t n_u
                       int32_t opt, float lr, float eps, const float* X, int64_t ld_x, float* g_wdense,
                       const dctr_dense_step_t* wdense_step, int32_t* workspace, int64_t workspace_ints,
                       int32_t presorted, dctr_stream_t stream, const dctr_lazy_unit_t* lz, const int32_t* lz_step,
-                      const dctr_lazy_opt_t* lz_opt);
-}  // namespace
-
-extern "C" int dctr_embed_update(const dctr_plan_t* plan, const int32_t* units, int32_t n_units,
-                                 int64_t max_vocab, const int32_t* ids_t, const uint16_t* parts_t, int32_t B,
-                                 const float* g_out,
-                                 int64_t ld_g, const float* out, int64_t ld_out, const float* fm_s,
-                                 int64_t ld_s, const float* g_fm, const float* g_wide, int64_t ld_gw,
-                                 int32_t opt, float lr, float eps, const float* X, int64_t ld_x, float* g_wdense,
-                                 const dctr_dense_step_t* wdense_step, int32_t* workspace, int64_t workspace_ints,
-                                 int32_t presorted, dctr_stream_t stream) {
-  if (opt == DCTR_UPD_LAZY) return DCTR_EINVAL;       // (dctr_embed_update_lazy)
-  return embed_update_impl(plan, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, ld_out, fm_s, ld_s, g_fm,
-                           g_wide, ld_gw, opt, lr, eps, X, ld_x, g_wdense, wdense_step, workspace, workspace_ints, presorted,
-                           stream, nullptr, nullptr, nullptr);
-}
-
-extern "C" int dctr_embed_update_lazy(const dctr_plan_t* plan, const int32_t* units, int32_t n_units, int64_t max_vocab,
-                                      const int32_t* ids_t, const uint16_t* parts_t, int32_t B, const float* g_out,
-                                      int64_t ld_g, const float* out, int64_t ld_out, const float* fm_s, int64_t ld_s,
-                                      const float* g_fm, const float* g_wide, int64_t ld_gw, const float* X, int64_t ld_x,
-                                      float* g_wdense, int32_t* workspace, int64_t workspace_ints,
-                                      const dctr_lazy_unit_t* lazy_units, const int32_t* step, const dctr_lazy_opt_t* lazy_opt,
-                                      dctr_stream_t stream) {
-  if (!lazy_units || !step || !lazy_opt) return DCTR_EINVAL;
-  if (plan && plan->ext) return DCTR_ENOSUP;            // (simple units only, like csrc/lazy.hip)
-  return embed_update_impl(plan, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, ld_out, fm_s, ld_s, g_fm,
-                           g_wide, ld_gw, DCTR_UPD_LAZY, 0.f, 0.f, X, ld_x, g_wdense, nullptr, workspace, workspace_ints, 1,
-                           stream, lazy_units, step, lazy_opt);
-}
-
-namespace {
-int embed_update_impl(const dctr_plan_t* plan, const int32_t* units, int32_t n_units,
-                      int64_t max_vocab, const int32_t* ids_t, const uint16_t* parts_t, int32_t B,
-                      const float* g_out,
-                      int64_t ld_g, const float* out, int64_t ld_out, const float* fm_s,
-                      int64_t ld_s, const float* g_fm, const float* g_wide, int64_t ld_gw,
-                      int32_t opt, float lr, float eps, const float* X, int64_t ld_x, float* g_wdense,
-                      const dctr_dense_step_t* wdense_step, int32_t* workspace, int64_t workspace_ints,
-                      int32_t presorted, dctr_stream_t stream, const dctr_lazy_unit_t* lz, const int32_t* lz_step,
                       const dctr_lazy_opt_t* lz_opt) {
   // (out / ld_out: the forward's rows.  Fixed-length fields never re-read them -- FM is folded algebraically at the row --
   // a POOLED field's FM backward needs its pooled value, which is no table row: general units read it there)
@@ -970,3 +902,31 @@ int embed_update_impl(const dctr_plan_t* plan, const int32_t* units, int32_t n_u
   return launch_status();
 }
 }  // namespace
+
+extern "C" int dctr_embed_update(const dctr_plan_t* plan, const int32_t* units, int32_t n_units,
+                                 int64_t max_vocab, const int32_t* ids_t, const uint16_t* parts_t, int32_t B,
+                                 const float* g_out,
+                                 int64_t ld_g, const float* out, int64_t ld_out, const float* fm_s,
+                                 int64_t ld_s, const float* g_fm, const float* g_wide, int64_t ld_gw,
+                                 int32_t opt, float lr, float eps, const float* X, int64_t ld_x, float* g_wdense,
+                                 const dctr_dense_step_t* wdense_step, int32_t* workspace, int64_t workspace_ints,
+                                 int32_t presorted, dctr_stream_t stream) {
+  if (opt == DCTR_UPD_LAZY) return DCTR_EINVAL;       // (dctr_embed_update_lazy)
+  return embed_update_impl(plan, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, ld_out, fm_s, ld_s, g_fm,
+                           g_wide, ld_gw, opt, lr, eps, X, ld_x, g_wdense, wdense_step, workspace, workspace_ints, presorted,
+                           stream, nullptr, nullptr, nullptr);
+}
+
+extern "C" int dctr_embed_update_lazy(const dctr_plan_t* plan, const int32_t* units, int32_t n_units, int64_t max_vocab,
+                                      const int32_t* ids_t, const uint16_t* parts_t, int32_t B, const float* g_out,
+                                      int64_t ld_g, const float* out, int64_t ld_out, const float* fm_s, int64_t ld_s,
+                                      const float* g_fm, const float* g_wide, int64_t ld_gw, const float* X, int64_t ld_x,
+                                      float* g_wdense, int32_t* workspace, int64_t workspace_ints,
+                                      const dctr_lazy_unit_t* lazy_units, const int32_t* step, const dctr_lazy_opt_t* lazy_opt,
+                                      dctr_stream_t stream) {
+  if (!lazy_units || !step || !lazy_opt) return DCTR_EINVAL;
+  if (plan && plan->ext) return DCTR_ENOSUP;            // (simple units only, like csrc/lazy.hip)
+  return embed_update_impl(plan, units, n_units, max_vocab, ids_t, parts_t, B, g_out, ld_g, out, ld_out, fm_s, ld_s, g_fm,
+                           g_wide, ld_gw, DCTR_UPD_LAZY, 0.f, 0.f, X, ld_x, g_wdense, nullptr, workspace, workspace_ints, 1,
+                           stream, lazy_units, step, lazy_opt);
+}

@@ -19,7 +19,7 @@
 //             rank sort of the keys runs in the shadow of those loads; gradients are parked in LDS at their
 //             SORTED position; the last entry of every id segment sums its segment backwards and
 //             read-modify-writes the row strips it already holds;
-//      else if they fit kCap: bitonic / rank sort, then tiles of G sorted entries with a carry;
+//      else if they fit kCap: rank sort, then tiles of G sorted entries with a carry;
 //   3. a partition with MORE than kCap entries (skewed ids) is split by the next bit of id / P and the two
 //             halves are processed one after the other (re-scanning the ids; LDS stays small); a half that still
 //             overflows but holds ONE id -- a hot id -- is summed by streaming over the batch in sample order.
@@ -419,7 +419,6 @@ __device__ __forceinline__ void gen_entry(const UpdArgs& A, const EntryDesc& E, 
   }
 }
 
-// One (unit, partition): scan (or take the bucket), sort, segment sums, one read-modify-write per touched row.
 // ---- where a tile's segments start, without a dependent LDS walk ---------------------------------------------------
 // Every wave publishes which of its groups end a segment (one ballot, before the tile's barrier); a summing group then
 // finds the first entry of its own segment from the flags strictly below it.  The walk over the segment becomes a
@@ -474,6 +473,46 @@ __device__ __forceinline__ int seg_first(const unsigned long long* tails, int ti
   return m ? wv * (64 / LPR) + (63 - __clzll(m)) / LPR + 1 : 0;
 }
 
+// ---- tag scan -------------------------------------------------------------------------------------------------------
+// The forward stored clamp(id) mod P next to every id: finding a partition's entries among a unit's B is a 16-bit compare
+// per entry (a workgroup keeps ~1/P of them).  keep(b) is called for every b with pt[b] == pp; all tag loads of a chunk are
+// issued before any is consumed (two vector loads in flight: one L2 round trip per chunk).  vec_ok: pt is 16-byte aligned
+// and B a multiple of 8.  (Was: a 64-bit reciprocal multiply per id, per workgroup -- 5.5 us of quarter-rate integer
+// multiplies at B = 4096; phase trace, round 1.)
+template <typename Keep>
+__device__ __forceinline__ void scan_tags(const uint16_t* pt, int B, bool vec_ok, uint32_t pp, Keep keep) {
+  const int tid = threadIdx.x;
+  if (vec_ok) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const DCTR_GLOBAL u32x4* pv = (const DCTR_GLOBAL u32x4*)pt;
+    const int nvec = B >> 3;
+    for (int c0 = 0; c0 < nvec; c0 += 2 * kThreads) {
+      u32x4 v[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int idx = c0 + q * kThreads + tid;
+        v[q] = pv[idx < nvec ? idx : 0];
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int idx = c0 + q * kThreads + tid;
+        if (idx < nvec) {
+          const uint32_t d[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if ((d[j] & 0xFFFFu) == pp) keep(8 * idx + 2 * j);
+            if ((d[j] >> 16) == pp) keep(8 * idx + 2 * j + 1);
+          }
+        }
+      }
+    }
+  } else {
+    for (int b = tid; b < B; b += kThreads)
+      if (static_cast<uint32_t>(*(const DCTR_GLOBAL uint16_t*)(pt + b)) == pp) keep(b);
+  }
+}
+
+// One (unit, partition): scan (or take the bucket), sort, segment sums, one read-modify-write per touched row.
 template <int VEC, int LPR, int OPT, bool GEN>
 __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, const int p, const dctr_uslot_t* sl) {
   constexpr int G = kThreads / LPR;   // lane groups per workgroup = entries per tile (a power of two)
@@ -660,12 +699,8 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
     // ---- scan: collect the entries of (partition p, id/P mod 2^mbits == mres) ------------------------------------
     // All id loads of a chunk are issued before any is consumed: the scan costs one L2 round trip per chunk.
     if (!bucketed && A.parts_t) {
-      // The forward stored clamp(id) mod P next to every id: the scan is a 16-bit compare per entry (a workgroup
-      // keeps ~1/P of them), the exact division runs only for the entries kept.  Was: a 64-bit reciprocal multiply
-      // per id, per workgroup -- 5.5 us of quarter-rate integer multiplies at B = 4096 (phase trace, round 1).
-      const uint16_t* pt = A.parts_t + static_cast<int64_t>(U.c0) * A.B;
-      const uint32_t pp = static_cast<uint32_t>(U.pu);
-      auto keep = [&](int b) {
+      // the tag compare per entry; the exact division runs only for the entries kept
+      scan_tags(A.parts_t + static_cast<int64_t>(U.c0) * A.B, B, (A.B & 7) == 0, static_cast<uint32_t>(U.pu), [&](int b) {
         const int32_t id = clamp_id(ldg_i32(ids + b), vocab);
         uint32_t idq, pu_;
         split_id<GEN>(A, U, static_cast<uint32_t>(id), idq, pu_);
@@ -673,35 +708,7 @@ __device__ __forceinline__ void upd_partition(const UpdArgs& A, const int u, con
           const int slot = atomicAdd(&n_sh, 1);  // LDS atomic; the order is fixed by the sort below
           if (slot < kCap) keys[slot] = (idq << U.vbits) | static_cast<uint32_t>(b);
         }
-      };
-      if ((A.B & 7) == 0) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const DCTR_GLOBAL u32x4* pv = (const DCTR_GLOBAL u32x4*)pt;
-        const int nvec = B >> 3;
-        for (int c0 = 0; c0 < nvec; c0 += 2 * kThreads) {
-          u32x4 v[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int idx = c0 + q * kThreads + tid;
-            v[q] = pv[idx < nvec ? idx : 0];
-          }
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int idx = c0 + q * kThreads + tid;
-            if (idx < nvec) {
-              const uint32_t d[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                if ((d[j] & 0xFFFFu) == pp) keep(8 * idx + 2 * j);
-                if ((d[j] >> 16) == pp) keep(8 * idx + 2 * j + 1);
-              }
-            }
-          }
-        }
-      } else {
-        for (int b = tid; b < B; b += kThreads)
-          if (static_cast<uint32_t>(*(const DCTR_GLOBAL uint16_t*)(pt + b)) == pp) keep(b);
-      }
+      });
     } else if (!bucketed) {
     // (no partition tags: simple units only -- a general unit's tags also say which positions are masked out, the host
     // always supplies them)
@@ -1060,9 +1067,8 @@ __global__ __launch_bounds__(kThreads, 5) void k_embed_update(UpdArgs A) {
 // and one read-modify-write per touched row.  No scan, no sort, no stack: 8 workgroups per CU (the general kernel
 // below: 5), so a saturating launch keeps ~1.6x more rows in flight.  Same tiling, same summation order as the general
 // kernel's tiled path: bit-identical results.  A partition whose count exceeds kBucket (a hot id: the pre-pass could not
-// sort it) takes the general path right here (scan, split by id bits, streaming of a hot id), and the last n_wdense
-// workgroups of the launch do the dense half of Linear.  (Both used to be a second launch, k_embed_update_overflow: 8 us
-// of launch + boundary + counter round trip on the step's critical chain for work that is almost always empty -- round 3.)
+// sort it) takes the general path right here (scan, split by id bits, streaming of a hot id), and the first n_wdense
+// workgroups of the launch do the dense half of Linear.
 template <int VEC, int LPR, int OPT, bool GEN>
 __global__ __launch_bounds__(kThreads, 5) void k_embed_apply_sorted(UpdArgs A) {
   step_priority();

@@ -4,7 +4,8 @@
     tools/isa_diff.py before.s after.s [more_after.s ...]
 
 Per kernel found on both sides: SAME or DIFF of the instruction stream (comments stripped, the compiler's local label
-numbers normalised) and of the register / LDS / scratch metadata.  A text comparison and nothing more.  Exit status 1 on
+numbers normalised) and of the register / LDS / scratch metadata (a DIFF is followed by a `->` line with the `after` side's
+line count and metadata).  A text comparison and nothing more.  Exit status 1 on
 any DIFF or on a kernel of `before.s` that no `after` file defines."""
 import re
 import sys
@@ -43,6 +44,8 @@ def main():
             verdict = "SAME" if (code, meta) == after[name] else "DIFF"
         bad += verdict != "SAME"
         print("%-8s %6d lines  %s  %s" % (verdict, len(code), " ".join(meta), name))
+        if verdict == "DIFF":
+            print("%-8s %6d lines  %s" % ("  ->", len(after[name][0]), " ".join(after[name][1])))
     return 1 if bad else 0
 
 
