@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -261,6 +261,11 @@ SIGNATURES = {
     "dctr_ccpm_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "dctr_ccpm_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P,
                                      _P]),
+    "dctr_log_transform_workspace_floats": (ctypes.c_size_t, [_I32, _I32, _I32, _I32]),
+    "dctr_log_transform_fwd_train": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32] + [_P] * 7 + [_I64, _P, _P, _P]),
+    "dctr_log_transform_fwd_eval": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32] + [_P] * 11 + [_I64, _P]),
+    "dctr_log_transform_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32] + [_P] * 7 + [_I64, _P, _I64] +
+                               [_P] * 8),
     "dctr_din_attn_supported": (ctypes.c_int, [_I32, _I32, _P, _I32, _P, _I32]),
     "dctr_din_attn_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32]),
     "dctr_din_attn_fwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32,

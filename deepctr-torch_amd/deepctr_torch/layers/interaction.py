@@ -2,6 +2,7 @@
 hand-written gfx950 kernel in ``libdctr_hip.so``.  Constructor signatures, input/output shapes,
 parameter names and error behaviour follow the reference so models and checkpoints drop in."""
 import itertools
+import os
 
 import torch
 import torch.nn as nn
@@ -12,7 +13,7 @@ from .activation import Identity, activation_layer
 from .core import Conv2dSame
 from .sequence import KMaxPooling
 
-__all__ = ["FM", "BiInteractionPooling", "AFMLayer", "InteractingLayer", "CrossNetMix", "CIN", "SENETLayer", "BilinearInteraction", "InnerProductLayer", "OutterProductLayer", "CrossNet", "ConvLayer", "ccpm_pool_sizes"]
+__all__ = ["FM", "BiInteractionPooling", "AFMLayer", "InteractingLayer", "CrossNetMix", "CIN", "SENETLayer", "BilinearInteraction", "InnerProductLayer", "OutterProductLayer", "CrossNet", "ConvLayer", "ccpm_pool_sizes", "LogTransformLayer"]
 
 
 class FM(nn.Module):
@@ -589,3 +590,79 @@ class ConvLayer(nn.Module):
         keep = torch.is_grad_enabled() and (inputs.requires_grad or params.requires_grad)
         out = _ops.CCPMConvFunction.apply(inputs.squeeze(1), params, tuple(widths), tuple(filters), tuple(ks), keep)
         return out.view(inputs.shape[0], filters[-1], ks[-1], inputs.shape[3])
+
+
+class LogTransformLayer(nn.Module):
+    """Logarithmic transformation layer of AFN: ``exp(BN(log|x|) W + b)`` per embedding channel, normalised again --
+    ``[B, field_size, embedding_size] -> [B, ltl_hidden_size * embedding_size]`` (reference interaction.py:720-757: same
+    constructor, initialisation order and keys ``ltl_weights``, ``ltl_biases [1, 1, H]``, ``bn.0.*``, ``bn.1.*``).
+
+    ``csrc/log_transform.hip``: nothing of size ``[B, E, H]`` exists but the output.  Train mode is three launches (BN0's
+    statistics, BN1's statistics from a recomputed ``exp`` that is never written, the output), eval mode one, the backward
+    three; the running statistics follow ``nn.BatchNorm1d``'s rule from the batch statistics the kernel returns, as
+    in-place device ops (nothing synchronises with the host).  Outside the kernel (``_kernel_fits``; anything but
+    float32; a gradient asked for in eval mode; ``DCTR_LOG_TRANSFORM=0``) ``_torch_route`` runs the reference's op
+    sequence as PyTorch-ROCm ops."""
+
+    def __init__(self, field_size, embedding_size, ltl_hidden_size):
+        super(LogTransformLayer, self).__init__()
+        self.ltl_weights = nn.Parameter(torch.Tensor(field_size, ltl_hidden_size))
+        self.ltl_biases = nn.Parameter(torch.Tensor(1, 1, ltl_hidden_size))
+        self.bn = nn.ModuleList([nn.BatchNorm1d(embedding_size) for i in range(2)])
+        nn.init.normal_(self.ltl_weights, mean=0.0, std=0.1)
+        nn.init.zeros_(self.ltl_biases, )
+
+    @staticmethod
+    def _kernel_fits(F, E, H):
+        """csrc/log_transform.hip: 1 <= F <= 64, 1 <= E <= 64, 1 <= H <= 1024 (include/dctr.h)."""
+        return 1 <= F <= 64 and 1 <= E <= 64 and 1 <= H <= 1024
+
+    def _torch_route(self, inputs):
+        afn_input = torch.clamp(torch.abs(inputs), min=1e-7, max=float("Inf"))
+        afn_input_trans = torch.transpose(afn_input, 1, 2)
+        ltl_result = torch.log(afn_input_trans)
+        ltl_result = self.bn[0](ltl_result)
+        ltl_result = torch.matmul(ltl_result, self.ltl_weights) + self.ltl_biases
+        ltl_result = torch.exp(ltl_result)
+        ltl_result = self.bn[1](ltl_result)
+        return torch.flatten(ltl_result, start_dim=1)
+
+    def _fused(self, inputs):
+        bn0, bn1 = self.bn
+        if os.environ.get("DCTR_LOG_TRANSFORM", "1") == "0" or inputs.dim() != 3 or inputs.dtype != torch.float32 or \
+                self.ltl_weights.dtype != torch.float32 or inputs.shape[1] != self.ltl_weights.shape[0] or \
+                inputs.shape[2] != bn0.num_features or \
+                not self._kernel_fits(inputs.shape[1], inputs.shape[2], self.ltl_weights.shape[1]):
+            return False
+        for bn in (bn0, bn1):
+            if not bn.affine or not bn.track_running_stats or bn.momentum is None or bn.eps != 1e-5:
+                return False
+        if not self.training:      # eval: one launch, no backward
+            return not (torch.is_grad_enabled() and (inputs.requires_grad or
+                                                     any(p.requires_grad for p in self.parameters())))
+        return True
+
+    def forward(self, inputs):
+        if not self._fused(inputs):
+            return self._torch_route(inputs)
+        bn0, bn1 = self.bn
+        B, F, E = inputs.shape
+        H = self.ltl_weights.shape[1]
+        train = self.training
+        if train and (B * F <= 1 or B * H <= 1):     # (nn.BatchNorm1d's own check)
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (
+                str(tuple(inputs.shape)),))
+        keep = train and torch.is_grad_enabled() and (inputs.requires_grad or
+                                                      any(p.requires_grad for p in self.parameters()))
+        out, stats = _ops.LogTransformFunction.apply(
+            inputs, self.ltl_weights, self.ltl_biases, bn0.weight, bn0.bias, bn1.weight, bn1.bias, bn0.running_mean,
+            bn0.running_var, bn1.running_mean, bn1.running_var, train, keep)
+        if train:
+            with torch.no_grad():
+                stats = stats.float()
+                for i, (bn, n) in enumerate(((bn0, B * F), (bn1, B * H))):
+                    m = float(bn.momentum)
+                    bn.num_batches_tracked.add_(1)
+                    bn.running_mean.mul_(1.0 - m).add_(stats[2 * i], alpha=m)
+                    bn.running_var.mul_(1.0 - m).add_(stats[2 * i + 1], alpha=m * n / (n - 1.0))
+        return out

@@ -1,6 +1,7 @@
 """Drop-in model classes of the MI355X hot path.  Constructor signatures
 and ``state_dict`` keys are the reference's (``deepctr_torch/models/*.py``)."""
 from .afm import AFM
+from .afn import AFN
 from .autoint import AutoInt
 from .basemodel import BaseModel, Linear
 from .ccpm import CCPM
@@ -20,4 +21,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN", "CCPM", "DIN", "DIEN", "SharedBottom", "ESMM", "MMOE", "PLE"]
+           "IFM", "DIFM", "ONN", "CCPM", "DIN", "DIEN", "AFN", "SharedBottom", "ESMM", "MMOE", "PLE"]

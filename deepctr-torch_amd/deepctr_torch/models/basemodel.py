@@ -1019,9 +1019,21 @@ class BaseModel(nn.Module):
             return 1
         return S
 
+    def _graph_mode(self):
+        """What a captured train step bakes in besides shapes: ``self.training`` when a layer behaves differently in the
+        two modes (BatchNorm, active dropout), else None.  Like the reference, ``fit()`` goes on training in eval mode after
+        the first validation pass; a step captured before it normalises with batch statistics and must not be replayed
+        after it."""
+        dep = self.__dict__.get("_mode_dependent")
+        if dep is None:
+            dep = self._mode_dependent = any(
+                isinstance(m, nn.modules.batchnorm._BatchNorm) or (isinstance(m, nn.Dropout) and m.p > 0)
+                for m in self.modules())
+        return self.training if dep else None
+
     def _fit_graph_ready(self, xb_like, S):
         g = self._fit_graph
-        if g is None or g.get("graph") is None or g["fused"] is not self._fused:
+        if g is None or g.get("graph") is None or g["fused"] is not self._fused or g.get("mode") != self._graph_mode():
             return None
         gr = g["graph"]
         return gr if (gr.S == S and gr.valid_for(xb_like)) else None
@@ -1037,11 +1049,14 @@ class BaseModel(nn.Module):
         g = self._fit_graph
         if xb.shape[0] != batch_size or not xb.is_cuda or os.environ.get("DCTR_FIT_GRAPH", "1") == "0":
             return self._train_step(xb, yb)
+        mode = self._graph_mode()
         if g is not None and g["graph"] is not None and g["graph"].valid_for(xb) and g["fused"] is self._fused and \
-                g["graph"].S == S:
+                g["graph"].S == S and g.get("mode") == mode:
             return g["graph"](xb, yb) if S == 1 else self._train_step(xb, yb)
-        if g is None or g.get("shape") != tuple(xb.shape) or g["fused"] is not self._fused or g.get("S", 1) != S:
-            g = self._fit_graph = {"shape": tuple(xb.shape), "warm": 0, "graph": None, "fused": self._fused, "S": S}
+        if g is None or g.get("shape") != tuple(xb.shape) or g["fused"] is not self._fused or g.get("S", 1) != S or \
+                g.get("mode") != mode:
+            g = self._fit_graph = {"shape": tuple(xb.shape), "warm": 0, "graph": None, "fused": self._fused, "S": S,
+                                   "mode": mode}
         out = self._train_step(xb, yb)              # eager warm-up steps (also builds the fused-step state)
         g["warm"] += 1
         g["fused"] = self._fused

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 32
+#define DCTR_ABI_VERSION 33
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -421,6 +421,46 @@ int dctr_ccpm_fwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D,
 int dctr_ccpm_bwd(const float* E, int64_t ld_e, int32_t B, int32_t F, int32_t D, int32_t n_layers, const int32_t* width,
                   const int32_t* filters, const int32_t* k, const float* params, const uint8_t* sel, const float* g_out,
                   int64_t ld_gout, float* gE, int64_t ld_ge, float* g_params, float* workspace, dctr_stream_t stream);
+
+/* ---- LogTransformLayer of AFN (interaction.py:720-757; csrc/log_transform.hip) -------------------------------------
+ * X [B, F, E] rows at X + b*ld_e (element (f, e) at f*E + e), W [F, H], bias [H], two BatchNorm1d(E) (eps 1e-5):
+ *   a[b,e,f] = log(max(|X[b,f,e]|, 1e-7f))
+ *   n[b,e,f] = bn0_w[e] * (a - mean0[e]) / sqrt(var0[e] + eps) + bn0_b[e]          statistics per e over (b, f)
+ *   z[b,e,h] = sum_f n[b,e,f] * W[f,h] + bias[h]        y = exp(z)
+ *   out[b, e*H + h] = bn1_w[e] * (y - mean1[e]) / sqrt(var1[e] + eps) + bn1_b[e]   statistics per e over (b, h)
+ * fwd_train: the statistics are the batch's (mean and BIASED variance, held to float64: per-workgroup (count, mean, M2)
+ *   merged by Chan's formula) and are returned in stats [4][E] = mean0 | var0 | mean1 | var1 as DOUBLES -- what is left
+ *   of a gradient after BatchNorm's backward projection is eps / (var + eps) of its terms, so a float rstd would move it
+ *   by 1e-7 / that; the kernels normalise in double.  The caller applies torch's running-statistics rule.  Three launches: BN0 partials; BN1 partials from a recomputed y that is never written; out.
+ * fwd_eval: one launch on the statistics handed in (the running ones).
+ * bwd (of fwd_train, given its stats): with yhat = (y - mean1) / sqrt(var1 + eps), N1 = B*H, N0 = B*F, g = g_out:
+ *   g_bn1_b[e] = sum g          g_bn1_w[e] = sum g * yhat                                            over (b, h)
+ *   gz = bn1_w * rstd1 * (g - g_bn1_b / N1 - yhat * g_bn1_w / N1) * y
+ *   gbias[h] = sum_{b,e} gz     gW[f,h] = sum_{b,e} n * gz     gn[b,e,f] = sum_h gz * W[f,h]
+ *   g_bn0_b[e] = sum gn         g_bn0_w[e] = sum gn * nhat      (nhat = (a - mean0) * rstd0)          over (b, f)
+ *   ga = bn0_w * rstd0 * (gn - g_bn0_b / N0 - nhat * g_bn0_w / N0)
+ *   gX[b,f,e] = ga / X[b,f,e] where |X| >= 1e-7f, 0 elsewhere        (rows at gX + b*ld_gx)
+ *   Three launches; g_out (rows at g_out + b*ld_g) is read twice, y is recomputed, nothing else of its size is touched.
+ * Every cross-workgroup sum is a fixed-order sum of per-workgroup partials (no atomics): identical bits run to run.
+ * workspace: dctr_log_transform_workspace_floats(B, F, E, H) floats (covers both directions; nothing is carried from the
+ * forward to the backward in it), 8-byte aligned (DCTR_EALIGN): the partials are doubles.  B == 0 returns DCTR_OK (the backward zeroes the parameter gradients).
+ * DCTR_ENOSUP unless 1 <= F <= 64, 1 <= E <= 64, 1 <= H <= 1024.  A workgroup (256 threads) owns one e, 32 samples at a
+ * time and 128 columns of H; static LDS: W slice 64 x 128 floats (32 KB) + n tile 32 x 65 (8.1 KB) + bias 0.5 KB forward,
+ * plus a second 32 x 65 tile and gz 32 x 129 (16.1 KB) in the backward's main pass: 41 KB / 66 KB, whatever the shape. */
+size_t dctr_log_transform_workspace_floats(int32_t B, int32_t F, int32_t E, int32_t H);
+int dctr_log_transform_fwd_train(const float* X, int64_t ld_e, int32_t B, int32_t F, int32_t E, int32_t H, const float* W,
+                                 const float* bias, const float* bn0_w, const float* bn0_b, const float* bn1_w,
+                                 const float* bn1_b, float* out, int64_t ld_out, double* stats, float* workspace,
+                                 dctr_stream_t stream);
+int dctr_log_transform_fwd_eval(const float* X, int64_t ld_e, int32_t B, int32_t F, int32_t E, int32_t H, const float* W,
+                                const float* bias, const float* bn0_w, const float* bn0_b, const float* bn0_mean,
+                                const float* bn0_var, const float* bn1_w, const float* bn1_b, const float* bn1_mean,
+                                const float* bn1_var, float* out, int64_t ld_out, dctr_stream_t stream);
+int dctr_log_transform_bwd(const float* X, int64_t ld_e, int32_t B, int32_t F, int32_t E, int32_t H, const float* W,
+                           const float* bias, const float* bn0_w, const float* bn0_b, const float* bn1_w,
+                           const double* stats, const float* g_out, int64_t ld_g, float* gX, int64_t ld_gx, float* gW,
+                           float* gbias, float* g_bn0_w, float* g_bn0_b, float* g_bn1_w, float* g_bn1_b, float* workspace,
+                           dctr_stream_t stream);
 
 /* ---- AttentionSequencePoolingLayer of DIN / DIEN (sequence.py:80-154 over core.py:10-64; csrc/din.hip) -----------------
  * Per sample, with query q [E], keys k_t [E] (t < T), hidden layers l = 1..n_layers of hidden[l-1] units:
