@@ -921,10 +921,14 @@ int dctr_crossnet_mix_bwd(const struct dctr_mlp* m, int32_t E, int32_t R, const 
  *     logit[b] = h_L[b, :] . w_out                              w_out = dnn_linear.weight [1, N_L]
  * The struct lives in HOST memory.  W rows are addressed W + n*ld_w with ld_w % 4 == 0 and a 16-byte aligned
  * base; floats in the row padding [K, ld_w) must be finite (they are multiplied by zero).  gW is written with
- * the same leading dimension (padding columns receive 0).
+ * the same leading dimension (padding columns receive 0).  Floats in x's row padding [K, ld_x) never enter a
+ * product (every kernel selects them away before it multiplies): they may hold anything, NaN included.
  *   h   [B, ld_h] post-activation output of the layer: written by dctr_mlp_fwd when non-NULL (needed by the
  *                 backward for every layer; without w_out the last layer's h IS the result)
  *   dh  [B, ld_h] backward scratch: d loss / d pre-activation, written by dctr_mlp_bwd
+ * Columns [N, ld_h) of h and dh are padding: those below round_up(N, 4) are set to 0 or left as they were, those
+ * from round_up(N, 4) on are never written.  Columns [K, ld_gx) of gx are padding: those below round_up(K, 32) are
+ * set to 0, those below round_up(K, 64) are set to 0 or left as they were, those from there on are never written.
  * dctr_mlp_bwd takes g = d loss / d logit [B] (with w_out) or d loss / d h_L [B, ld_g] (without) and writes
  *   gx [B, ld_gx] = d loss / d x (nullable), layer[l].gW, layer[l].gbias, g_w_out.
  * Replaces autograd's mm / addmm / threshold_backward / sum chains under basemodel.py:261.  Everything is

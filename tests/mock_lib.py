@@ -60,6 +60,8 @@ class _Core(object):
     def dctr_mlp_fwd(self, mref, x, ld_x, B, logit, stream):
         self.calls.append("mlp_fwd")
         m, layers = self._layers(mref)
+        if B <= 0:
+            return 0
         h = _arr(x, (B, layers[0].K), ld_x).astype(np.float64)
         for e in layers:
             W = _arr(e.W, (e.N, e.K), e.ld_w).astype(np.float64)
@@ -80,6 +82,8 @@ class _Core(object):
     def dctr_mlp_bwd(self, mref, x, ld_x, B, g, ld_g, gx, ld_gx, ws, stream):
         self.calls.append("mlp_bwd")
         m, layers = self._layers(mref)
+        if B <= 0:
+            return 0
         top = layers[-1]
         if m.w_out:
             gh = np.outer(_arr(g, (B,)).astype(np.float64), _arr(m.w_out, (top.N,)).astype(np.float64))
@@ -97,11 +101,15 @@ class _Core(object):
                 full = _arr(e.gW, (e.N, e.ld_w), e.ld_w)
                 full[...] = 0
                 full[:, :e.K] = gh.T @ inp.astype(np.float64)
-            if e.gbias:
+            if e.gbias and e.bias:          # (launch_wgrad_reduce hands a layer without bias no destination)
                 _arr(e.gbias, (e.N,))[...] = gh.sum(0)
             gh = gh @ _arr(e.W, (e.N, e.K), e.ld_w).astype(np.float64)
         if gx:
-            _arr(gx, (B, layers[0].K), ld_gx)[...] = gh
+            # include/dctr.h: columns [K, ld_gx) up to the next multiple of 32 receive 0
+            K = layers[0].K
+            full = _arr(gx, (B, min(int(ld_gx), (K + 31) // 32 * 32)), ld_gx)
+            full[...] = 0
+            full[:, :K] = gh
         return 0
 
     def dctr_mlp_train_workspace_floats(self, mref, B):
@@ -132,29 +140,38 @@ class _Core(object):
             _arr(loss, (1,))[0] = hp[0]
             if g_bias is not None and getattr(g_bias, "value", g_bias):
                 _arr(g_bias, (1,))[0] = hp[1]
-        if step is not None:
+        if step is not None and B > 0:
             self.calls.append("mlp_train_wgrad+step")
-            m, layers = self._layers(mref)
-            for e in layers:
-                self._dense_step(step, e.gW, e.N * e.ld_w)
-                if e.bias and e.gbias:
-                    self._dense_step(step, e.gbias, e.N)
-            if m.g_w_out:
-                self._dense_step(step, m.g_w_out, layers[-1].N)
-            if g_bias is not None and getattr(g_bias, "value", g_bias):
-                self._dense_step(step, g_bias, 1)
+            self._tower_step(mref, g_bias, step)
         return 0
+
+    def _tower_step(self, mref, g_bias, step):
+        """the in-kernel optimizer of the reduction that finishes the tower's gradients (include/dctr.h)"""
+        m, layers = self._layers(mref)
+        for e in layers:
+            self._dense_step(step, e.gW, e.N * e.ld_w)
+            if e.bias and e.gbias:
+                self._dense_step(step, e.gbias, e.N)
+        if m.g_w_out:
+            self._dense_step(step, m.g_w_out, layers[-1].N)
+        if g_bias is not None and getattr(g_bias, "value", g_bias):
+            self._dense_step(step, g_bias, 1)
 
     def dctr_mlp_train_step(self, mref, x, ld_x, B, p0, p1, bias, y, y_pred, loss, g_logit, g_bias, gx, ld_gx, ws,
                             defer_wgrad, step, stream):
         """forward + head + backward in one call, composed from the pieces above."""
         import torch
+        if B <= 0:
+            self.calls.append("mlp_train_step")
+            return 0
         logit = torch.zeros(B)
         lp = ctypes.c_void_p(logit.data_ptr())
         self.dctr_mlp_fwd(mref, x, ld_x, B, lp, stream)
         self.dctr_bce_head(p0, p1, lp, None, bias, y, B, y_pred, loss, g_logit, g_bias, stream)
         self.dctr_mlp_bwd(mref, x, ld_x, B, g_logit, 0, gx, ld_gx, ws, stream)
         self.calls = self.calls[:-3] + ["mlp_train_step"]
+        if step is not None and not defer_wgrad:          # (the reduction's optimizer step, as dctr_mlp_train_wgrad applies it)
+            self._tower_step(mref, g_bias, step)
         return 0
 
     def dctr_embed_tower_train_supported(self, pref, mref, B):
