@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -103,6 +103,14 @@ class Gate(ctypes.Structure):
                 ("member", ctypes.c_int32 * GATE_MAX_MEMBERS)]
 
 
+class Mlr(ctypes.Structure):
+    """``dctr_mlr_t`` (include/dctr.h): the heads of an MLR plan -- host struct, device arrays."""
+    _fields_ = [("head_of", ctypes.c_void_p), ("dense_cols", ctypes.c_void_p), ("dense_off", ctypes.c_void_p),
+                ("dense_w", ctypes.c_void_p), ("n_regions", ctypes.c_int32), ("has_bias", ctypes.c_int32),
+                ("task", ctypes.c_int32), ("n_dense", ctypes.c_int32)]
+
+
+MLR_BINARY, MLR_REGRESSION, MLR_MAX_REGIONS = 0, 1, 16
 PLAN_HAS_GACC, PLAN_HAS_STATE, PLAN_HAS_MAXPOOL, PLAN_WIDE_PER_FIELD = 1, 2, 4, 8
 IAFM_SOFTMAX, IAFM_SUM = 0, 1
 LAZY_SGD, LAZY_ADAGRAD, LAZY_ADAM, LAZY_RMSPROP = 0, 1, 2, 3
@@ -282,6 +290,13 @@ SIGNATURES = {
     "dctr_gate_mix_bwd_workspace_floats": (ctypes.c_size_t, [_I32, _I32, _P, _P]),
     "dctr_gate_mix_fwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P]),
     "dctr_gate_mix_bwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "dctr_sizeof_mlr": (ctypes.c_size_t, []),
+    "dctr_mlr_supported": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.POINTER(Mlr)]),
+    "dctr_mlr_fwd": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.POINTER(Mlr), _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _P,
+                                    _I32, _P]),
+    "dctr_mlr_bwd_workspace_floats": (ctypes.c_size_t, [ctypes.POINTER(Mlr), _I32]),
+    "dctr_mlr_bwd": (ctypes.c_int, [ctypes.POINTER(Plan), ctypes.POINTER(Mlr), _P, _I64, _I32, _P, _P, _I64, _P, _I64, _P,
+                                    _P, _P]),
     "dctr_bi_pooling_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "dctr_bi_pooling_bwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _I64, _P]),
 }
@@ -338,7 +353,8 @@ def lib():
                 or handle.dctr_sizeof_lazy_opt() != ctypes.sizeof(LazyOpt) \
                 or handle.dctr_sizeof_dense_step() != ctypes.sizeof(DenseStep) \
                 or handle.dctr_sizeof_dense_item() != ctypes.sizeof(DenseItem) \
-                or handle.dctr_sizeof_gate() != ctypes.sizeof(Gate):
+                or handle.dctr_sizeof_gate() != ctypes.sizeof(Gate) \
+                or handle.dctr_sizeof_mlr() != ctypes.sizeof(Mlr):
             raise RuntimeError("dctr_field_t / dctr_plan_t / dctr_mlp_t layout mismatch between header and binding")
         _lib = handle
     return _lib

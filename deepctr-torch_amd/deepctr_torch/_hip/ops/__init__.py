@@ -11,5 +11,6 @@ from .embed import (EmbedFunction, PairEmbedFunction, SplitGatheredFunction, emb
 from .fm import AFMFunction, BiPoolFunction, FMFunction, IAFMFunction, iafm, iafm_supported  # noqa: F401
 from .gate_mix import GateMixFunction, gate_mix, gate_mix_fused, gate_mix_torch  # noqa: F401
 from .log_transform import LogTransformFunction  # noqa: F401
+from .mlr import MLRFunction, MLRHeads, mlr, mlr_composed, mlr_route  # noqa: F401
 from .pairwise import (BilinearFunction, BilinearMeta, BilinearStackedFunction, InnerProductFunction,  # noqa: F401
                        SENETFunction, disjoint_groups, slab_ld, tournament_schedule)

@@ -390,11 +390,17 @@ class EmbeddingPlan(object):
     of ONN's pair p (csrc/pair_embed.hip).  The lookup's output row is then ``[P products of D | dense]``
     (``width = P * D + n_dense``, ``ld_out`` follows it) while a field's ``out_off`` is its offset in a ROW-GRADIENT row of
     ``2 P D`` floats (stride ``ld_rows``): what the pair backward writes and the update kernels read as their ``g_out``.
+
+    ``wide_sides``: the wide side as an explicit list of ``(columns, tables)`` -- several ``Linear`` modules side by side
+    (MLR's regions and bias, csrc/mlr.hip) -- instead of ``wide_columns`` over ``wide_tables``.  Each side goes through
+    ``_fields_for`` like a single one; the plan holds every side's fixed-length fields (side after side), then every side's
+    pooled VarLen fields.  ``head_of[f]`` is the side of wide field f, ``side_dense_cols[h]`` the X columns of side h's
+    dense features (their weights stay with the caller: such a plan has no ``wide_dense_weight``).
     """
 
     def __init__(self, feature_index, deep_columns=(), deep_tables=None, wide_columns=(), wide_tables=None,
                  wide_dense_weight=None, unpooled=False, with_dense=True, wide_per_field=False, deep_fields=None,
-                 pair=False):
+                 pair=False, wide_sides=None):
         self.feature_index = feature_index
         self.wide_per_field = bool(wide_per_field)
         self.pair = bool(pair)
@@ -417,8 +423,24 @@ class EmbeddingPlan(object):
             if deep_fields is None or len(dfix) % 2 or len(set(f.dim for f in dfix)) > 1 or self.wide_per_field:
                 raise ValueError("a pair plan takes an even number of explicit deep fields of one common dim "
                                  "(and no per-field wide side)")
-        wfix, wpool, _ = _fields_for(wide_columns, wide_tables, feature_index, False) \
-            if wide_tables is not None else ([], [], 0)
+        self.head_of = None
+        self.side_dense_cols = None
+        if wide_sides is not None:
+            if wide_tables is not None or len(wide_columns) or wide_dense_weight is not None:
+                raise ValueError("wide_sides and wide_columns / wide_tables / wide_dense_weight are two ways to name the "
+                                 "wide side: give one")
+            wfix, wpool, hfix, hpool, self.side_dense_cols = [], [], [], [], []
+            for h, (cols, tables) in enumerate(wide_sides):
+                fx, pl, _ = _fields_for(cols, tables, feature_index, False)
+                wfix += fx
+                wpool += pl
+                hfix += [h] * len(fx)
+                hpool += [h] * len(pl)
+                self.side_dense_cols.append([c for fc in split_columns(cols)[2] for c in range(*feature_index[fc.name])])
+            self.head_of = hfix + hpool
+        else:
+            wfix, wpool, _ = _fields_for(wide_columns, wide_tables, feature_index, False) \
+                if wide_tables is not None else ([], [], 0)
         self.deep = dfix + dpool
         self.wide = wfix + wpool
         self.n_deep_fixed, self.n_wide_fixed = len(dfix), len(wfix)
@@ -631,6 +653,8 @@ class EmbeddingPlan(object):
         self.__dict__.setdefault("pair", False)
         self.__dict__.setdefault("ld_rows", 0)
         self.__dict__.setdefault("unpooled_columns", ())
+        self.__dict__.setdefault("head_of", None)
+        self.__dict__.setdefault("side_dense_cols", None)
         self._reset_device_image()
 
     # ---- sparse-update mode (see ops/embed.py) ---------------------------------------------------------

@@ -13,6 +13,7 @@ from .difm import DIFM
 from .din import DIN
 from .fibinet import FiBiNET
 from .ifm import IFM
+from .mlr import MLR
 from .multitask import ESMM, MMOE, PLE, SharedBottom
 from .nfm import NFM
 from .onn import ONN
@@ -21,4 +22,4 @@ from .wdl import WDL
 from .xdeepfm import xDeepFM
 
 __all__ = ["BaseModel", "Linear", "DeepFM", "xDeepFM", "FiBiNET", "DCN", "PNN", "NFM", "AFM", "WDL", "AutoInt", "DCNMix",
-           "IFM", "DIFM", "ONN", "CCPM", "DIN", "DIEN", "AFN", "SharedBottom", "ESMM", "MMOE", "PLE"]
+           "IFM", "DIFM", "ONN", "CCPM", "DIN", "DIEN", "AFN", "MLR", "SharedBottom", "ESMM", "MMOE", "PLE"]

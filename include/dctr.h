@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 33
+#define DCTR_ABI_VERSION 34
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -380,6 +380,51 @@ int dctr_pair_embed_fwd(const dctr_plan_t* plan, const float* X, int64_t ldx, in
                         float* wide, int64_t ld_wide, int32_t* err, dctr_stream_t stream);
 int dctr_pair_embed_bwd(const dctr_plan_t* plan, const float* X, int64_t ldx, int32_t B, const float* g_out, int64_t ld_g,
                         float* g_rows, int64_t ld_rows, dctr_stream_t stream);
+
+/* ---- MLR / LS-PLM: the piece-wise linear mixture (models/mlr.py:78-100; csrc/mlr.hip) -------------------------------
+ * R region Linear modules are a softmax gate and, read again, the learners; an optional bias Linear scales the result:
+ *   z_h  = sum of head h's first-order weights (fixed-length fields, then pooled VarLen ones, in plan order)
+ *          + sum_j X[b, dense_cols[j]] * dense_w[h][j - dense_off[h]]   for j in [dense_off[h], dense_off[h + 1])
+ *   s    = softmax(z_0 .. z_{R-1})  (max-subtracted);   l_r = sigmoid(z_r) (DCTR_MLR_BINARY) | z_r (DCTR_MLR_REGRESSION)
+ *   p0   = sum_r s_r l_r;   c = sigmoid(z_R) when has_bias, else 1;   y = p0 * c
+ * The plan is wide-only (n_deep = 0, no dense block, no wdense_w) with DCTR_PLAN_WIDE_PER_FIELD: wide field f belongs to
+ * head head_of[f]; heads 0 .. R-1 are the regions, head R the bias.  A head without fields and a head without dense
+ * columns are ordinary.  H = n_regions + has_bias.
+ * forward, one launch: the gather's workgroup geometry (64 samples, 4 waves that split the fields), X rows and descriptors
+ *   staged in LDS once, 8 weight loads in flight per lane; VarLen fields pooled by the gather's device code (a max pool's
+ *   arg-max byte goes to ext->amax at am_wide_off[f]).  y [B]; z [B, ld_z >= H] keeps the H logits for the backward.
+ *   err: bit 0 is set when an id falls outside [0, vocab); such a row reads as row 0 (nullable).  ids_t / parts_t / units /
+ *   n_units: the side outputs of dctr_embed_fwd for the sorted update (nullable; NULL for a plan with ext).  Nothing of
+ *   size [B, n_wide] is written.  A sample's y and z depend neither on B nor on its position in the batch.
+ * backward (recomputes s, l, c from z), g = g_y[b]:
+ *   g_z[b, r] = g * c * (s_r (l_r - p0) + s_r l_r (1 - l_r))   (regression: the second term is s_r)
+ *   g_z[b, R] = g * p0 * c * (1 - c)
+ *   g_wide[b * ld_gw + f] = g_z[b, head_of[f]] for f < n_wide, g_wide[b * ld_gw + n_wide] = 0 (ld_gw >= n_wide + 1): the
+ *   per-field layout dctr_embed_update / _update_lazy / _bwd read (nullable when n_wide = 0)
+ *   g_dense[j] = sum_b g_z[b, head(j)] * X[b, dense_cols[j]]  for j < n_dense (nullable when n_dense = 0): per-tile partials
+ *   in ws (dctr_mlr_bwd_workspace_floats(mlr, B) floats), added in tile order by a second launch.  No atomics: every
+ *   output is bit-identical run to run.
+ * dctr_mlr_supported: 1 when both entry points take (plan, mlr); they return DCTR_ENOSUP otherwise: a deep side or a dense
+ * block, no DCTR_PLAN_WIDE_PER_FIELD, wdense_w, out_chunks, n_regions outside [2, 16], a tile beyond the LDS.          */
+#define DCTR_MLR_BINARY 0
+#define DCTR_MLR_REGRESSION 1
+#define DCTR_MLR_MAX_REGIONS 16
+typedef struct {
+  const int32_t* head_of;      /* device [n_wide]                                                                     */
+  const int32_t* dense_cols;   /* device [n_dense]: X columns of every head's dense features, head after head         */
+  const int32_t* dense_off;    /* device [H + 1]: head h owns dense_cols[dense_off[h] .. dense_off[h + 1])             */
+  const float* const* dense_w; /* device [H]: each head's Linear.weight (separate parameters; NULL without dense cols) */
+  int32_t n_regions, has_bias, task, n_dense;
+} dctr_mlr_t;
+size_t dctr_sizeof_mlr(void);
+int dctr_mlr_supported(const dctr_plan_t* plan, const dctr_mlr_t* mlr);
+int dctr_mlr_fwd(const dctr_plan_t* plan, const dctr_mlr_t* mlr, const float* X, int64_t ldx, int32_t B, float* y, float* z,
+                 int64_t ld_z, int32_t* err, int32_t* ids_t, uint16_t* parts_t, const int32_t* units, int32_t n_units,
+                 dctr_stream_t stream);
+size_t dctr_mlr_bwd_workspace_floats(const dctr_mlr_t* mlr, int32_t B);
+int dctr_mlr_bwd(const dctr_plan_t* plan, const dctr_mlr_t* mlr, const float* X, int64_t ldx, int32_t B, const float* g_y,
+                 const float* z, int64_t ld_z, float* g_wide, int64_t ld_gw, float* g_dense, float* ws,
+                 dctr_stream_t stream);
 
 /* ---- AFMLayer (interaction.py:251-325): attentional pooling of the pairwise products (csrc/afm.hip) -----------
  *   bi_k = e_i (.) e_j (pairs i < j, itertools.combinations order);  t_k = relu(bi_k W + bias);  s_k = t_k . h;
