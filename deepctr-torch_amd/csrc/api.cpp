@@ -13,6 +13,7 @@ extern "C" size_t dctr_sizeof_plan_ext(void) { return sizeof(dctr_plan_ext_t); }
 extern "C" size_t dctr_sizeof_mlp(void) { return sizeof(dctr_mlp_t); }
 extern "C" size_t dctr_sizeof_dense_step(void) { return sizeof(dctr_dense_step_t); }
 extern "C" size_t dctr_sizeof_dense_item(void) { return sizeof(dctr_dense_item_t); }
+extern "C" size_t dctr_sizeof_dense_item2(void) { return sizeof(dctr_dense_item2_t); }
 extern "C" size_t dctr_sizeof_gate(void) { return sizeof(dctr_gate_t); }
 extern "C" size_t dctr_sizeof_mlr(void) { return sizeof(dctr_mlr_t); }
 

@@ -9,6 +9,7 @@
 // addcdiv = 5-8 launches) with one pass over one flat slab (deepctr_torch/_hip/dense.py re-seats the parameters
 // as views of that slab).
 #include "common.hpp"
+#include "lazy_opt.hpp"
 
 using namespace dctr;
 
@@ -164,6 +165,76 @@ __global__ __launch_bounds__(256) void k_dense_opt_multi(MultiArgs A) {
           pv = sgd_param(pv, gv, A.lr);
         }
         stg_f32(p + j, pv);
+      }
+    }
+  }
+}
+
+// The same launch shape for Adam / RMSprop (and SGD / Adagrad) with a DEVICE-side step count: torch.optim.Adam computes
+// its bias corrections on the host, so its step cannot be replayed from a hipGraph; here the step number is *step + 1, read
+// by the kernel (dctr_lazy_step_inc advances it once after the last launch of a step).  The per-element arithmetic is
+// dctr_lazy::opt_step (lazy_opt.hpp, IEEE division / square root: the step carries a data gradient) -- the statement of
+// Adam / RMSprop that the lazy table update pins against the reference's trajectories -- with its multiply-adds pinned
+// (opt_step<., PIN>): the vector path and the per-element path of this kernel must give the same bits.
+struct MultiRegArgs {
+  float* p[kMulti];
+  const float* g[kMulti];
+  float* s1[kMulti];          // Adagrad sum | Adam exp_avg | RMSprop square_avg (a kind without it: p, never touched)
+  float* s2[kMulti];          // Adam exp_avg_sq (else: p, never touched)
+  long long n[kMulti];
+  float c2[kMulti];
+  int blk0[kMulti + 1];
+  int n_items;
+};
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_dense_opt_multi_reg(MultiRegArgs A, const int32_t* __restrict__ step_ptr,
+                                                             dctr_lazy::OptConst o) {
+  constexpr bool kS1 = KIND != DCTR_LAZY_SGD, kS2 = KIND == DCTR_LAZY_ADAM;
+  int t = 0;
+  const int blk = blockIdx.x;
+  while (t + 1 < A.n_items && blk >= A.blk0[t + 1]) ++t;
+  float* __restrict__ p = A.p[t];
+  const float* __restrict__ g = A.g[t];
+  float* __restrict__ s1 = A.s1[t];
+  float* __restrict__ s2 = A.s2[t];
+  const long long n = A.n[t];
+  const float c2 = A.c2[t];
+  const long long base = static_cast<long long>(blk - A.blk0[t]) * kChunk;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+                         reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(s2)) & 15u) == 0;
+  o.kind = KIND;
+  float ss = 0.f, bc = 1.f;
+  if (KIND == DCTR_LAZY_ADAM) dctr_lazy::adam_scalars(o, *(const DCTR_GLOBAL int32_t*)step_ptr + 1, ss, bc);
+#pragma unroll
+  for (int r = 0; r < kChunk / 1024; ++r) {
+    const long long i = base + r * 1024 + 4 * threadIdx.x;
+    if (i >= n) break;
+    if (aligned && i + 4 <= n) {
+      f32x4 pv = *(const DCTR_GLOBAL f32x4*)(p + i);
+      f32x4 gv = *(const DCTR_GLOBAL f32x4*)(g + i);
+      f32x4 av = {0.f, 0.f, 0.f, 0.f}, bv = {0.f, 0.f, 0.f, 0.f};
+      if (kS1) av = *(const DCTR_GLOBAL f32x4*)(s1 + i);
+      if (kS2) bv = *(const DCTR_GLOBAL f32x4*)(s2 + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float gk = gv[k], wk = pv[k], ak = av[k], bk = bv[k];
+        if (c2 != 0.f) gk = dctr_lazy::l2_grad_pinned(gk, c2, wk);     // (two roundings, no fma: contraction off)
+        dctr_lazy::opt_step<false, true>(o, gk, wk, ak, bk, ss, bc);
+        pv[k] = wk; av[k] = ak; bv[k] = bk;
+      }
+      if (kS1) *(DCTR_GLOBAL f32x4*)(s1 + i) = av;
+      if (kS2) *(DCTR_GLOBAL f32x4*)(s2 + i) = bv;
+      *(DCTR_GLOBAL f32x4*)(p + i) = pv;
+    } else {
+      for (long long j = i; j < i + 4 && j < n; ++j) {
+        float gk = ldg_f32(g + j), wk = ldg_f32(p + j);
+        float ak = kS1 ? ldg_f32(s1 + j) : 0.f, bk = kS2 ? ldg_f32(s2 + j) : 0.f;
+        if (c2 != 0.f) gk = dctr_lazy::l2_grad_pinned(gk, c2, wk);
+        dctr_lazy::opt_step<false, true>(o, gk, wk, ak, bk, ss, bc);
+        if (kS1) stg_f32(s1 + j, ak);
+        if (kS2) stg_f32(s2 + j, bk);
+        stg_f32(p + j, wk);
       }
     }
   }
@@ -343,6 +414,48 @@ extern "C" int dctr_dense_opt_multi(const dctr_dense_item_t* items, int32_t n_it
       const dim3 grid(static_cast<unsigned>(blocks)), block(256);
       if (opt == DCTR_UPD_ADAGRAD) k_dense_opt_multi<DCTR_UPD_ADAGRAD><<<grid, block, 0, s>>>(a);
       else k_dense_opt_multi<DCTR_UPD_SGD><<<grid, block, 0, s>>>(a);
+      const int stt = launch_status();
+      if (stt != DCTR_OK) return stt;
+    }
+    i0 += k;
+  }
+  return DCTR_OK;
+}
+
+extern "C" int dctr_dense_opt_multi_reg(const dctr_dense_item2_t* items, int32_t n_items, const dctr_lazy_opt_t* opt,
+                                        const int32_t* step, dctr_stream_t stream) {
+  if (n_items < 0 || (n_items > 0 && !items) || !opt || !step) return DCTR_EINVAL;
+  const int kind = opt->kind;
+  if (kind != DCTR_LAZY_SGD && kind != DCTR_LAZY_ADAGRAD && kind != DCTR_LAZY_ADAM && kind != DCTR_LAZY_RMSPROP)
+    return DCTR_EINVAL;
+  const bool need1 = kind != DCTR_LAZY_SGD, need2 = kind == DCTR_LAZY_ADAM;
+  for (int i = 0; i < n_items; ++i) {        // the whole list first: a refused call has launched nothing
+    const dctr_dense_item2_t& it = items[i];
+    if (it.n < 0 || (it.n > 0 && (!it.p || !it.g || (need1 && !it.s1) || (need2 && !it.s2)))) return DCTR_EINVAL;
+  }
+  const dctr_lazy::OptConst o = dctr_lazy::opt_const(opt);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < n_items;) {
+    MultiRegArgs a;
+    int k = 0;
+    long long blocks = 0;
+    for (; k < kMulti && i0 + k < n_items; ++k) {
+      const dctr_dense_item2_t& it = items[i0 + k];
+      const long long nb = (it.n + kChunk - 1) / kChunk;
+      if (blocks + nb > 0x7FFFFFF0ll) return DCTR_ENOSUP;
+      a.p[k] = it.p; a.g[k] = it.g; a.s1[k] = need1 ? it.s1 : it.p; a.s2[k] = need2 ? it.s2 : it.p; a.n[k] = it.n;
+      a.c2[k] = 2.f * it.l2;
+      a.blk0[k] = static_cast<int>(blocks);
+      blocks += nb;
+    }
+    a.blk0[k] = static_cast<int>(blocks);
+    a.n_items = k;
+    if (blocks > 0) {
+      const dim3 grid(static_cast<unsigned>(blocks)), block(256);
+      if (kind == DCTR_LAZY_ADAM) k_dense_opt_multi_reg<DCTR_LAZY_ADAM><<<grid, block, 0, s>>>(a, step, o);
+      else if (kind == DCTR_LAZY_RMSPROP) k_dense_opt_multi_reg<DCTR_LAZY_RMSPROP><<<grid, block, 0, s>>>(a, step, o);
+      else if (kind == DCTR_LAZY_ADAGRAD) k_dense_opt_multi_reg<DCTR_LAZY_ADAGRAD><<<grid, block, 0, s>>>(a, step, o);
+      else k_dense_opt_multi_reg<DCTR_LAZY_SGD><<<grid, block, 0, s>>>(a, step, o);
       const int stt = launch_status();
       if (stt != DCTR_OK) return stt;
     }

@@ -82,7 +82,7 @@ __device__ __forceinline__ void replay_in_step(const OptConst& o, float lam2d, f
 #pragma unroll
           for (int i = 0; i < VEC; i += 2) {
             f32x2 w2 = {w[i], w[i + 1]}, a2 = {a[i], a[i + 1]}, b2 = {b[i], b[i + 1]};
-            adam_replay_step<f32x2>(1.f - o.beta1, 1.f - o.beta2, o.beta2, o.eps, w2 * lam2d, ss, rbc, w2, a2, b2);
+            adam_replay_step<f32x2>(o.c1, o.c2, o.beta2, o.eps, w2 * lam2d, ss, rbc, w2, a2, b2);
             w[i] = w2.x; w[i + 1] = w2.y; a[i] = a2.x; a[i + 1] = a2.y; b[i] = b2.x; b[i + 1] = b2.y;
           }
         } else {

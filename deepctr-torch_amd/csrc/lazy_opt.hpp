@@ -16,6 +16,10 @@ constexpr bool kFastReplay = true;
 struct OptConst {
   int kind;   // DCTR_LAZY_SGD / ADAGRAD / ADAM / RMSPROP
   float lr, eps, beta1, beta2;
+  // Adam: the weights of the new gradient in the two moments, 1 - beta1 and 1 - beta2.  1.f - beta (what the kernels computed
+  // themselves before ABI 35: the same float subtraction, the same bits) unless the host hands over the values torch
+  // rounds from DOUBLE (dctr_lazy_opt_t.beta1_c / beta2_c): float(0.999) is 1.3e-8 off, which is 1.3e-5 of 1 - beta2
+  float c1, c2;
   // Adam's step-dependent scalars by step number (dctr_lazy_opt_t: adam_ss[T - 1], adam_bc[T - 1]; constant from the last
   // entry on), or NULL: computed in the kernel (AdamClock)
   const float* adam_ss;
@@ -150,14 +154,61 @@ __device__ __forceinline__ void adam_replay_step(float c1, float c2, float beta2
 
 // one optimizer step on one element.  a = Adagrad sum | Adam exp_avg, b = Adam exp_avg_sq.  FAST: the replay loop's
 // division / square root (above); rbc = rcp(bc2s), computed once per step by the caller.
-template <bool FAST = false>
+// PIN (the multi-tensor dense step, csrc/head.hip): the roundings of the FOREACH kernels torch.optim.Adam / RMSprop run on
+// the GPU (_foreach_lerp_, _foreach_mul_ + _foreach_addcmul_, _foreach_sqrt / div / add, _foreach_addcdiv_), measured
+// operation by operation on an MI355X, in their aligned and unaligned code paths alike: lerp is fma(w, g - a, a); addcmul
+// squares the gradient FIRST, fma(value, g * g, v), where the single-tensor kernel (and the reference's CPU run the tables
+// are pinned to) multiplies (value * g) * g; addcdiv is fma(value, a / d, p); sqrt and division are IEEE.  Written with
+// contraction OFF and every fused operation spelled out, and with sqrtf(), not __fsqrt_rn(): without
+// OCML_BASIC_ROUNDED_OPERATIONS the HIP header maps __fsqrt_rn to the 1-ulp hardware square root and __fadd_rn / __fmul_rn
+// to plain + and *, which the compiler contracts where it likes (it fused `a + (g - a) * c` in the vector path of one
+// kernel and not in its per-element path).  With these roundings a model whose gradients amplify one ulp (AFM) trains the
+// same under this step and under torch.optim.  Every other caller keeps its statement and its bits.
+__device__ __forceinline__ float l2_grad_pinned(float g, float c2, float w) {   // autograd: g + (2 lambda) * p, two roundings
+#pragma clang fp contract(off)
+  const float t = c2 * w;
+  return g + t;
+}
+__device__ __forceinline__ void opt_step_pinned(const OptConst& o, float g, float& w, float& a, float& b, float step_size,
+                                                float bc2s) {
+#pragma clang fp contract(off)
+  if (o.kind == DCTR_LAZY_ADAM) {
+    const float d = g - a;
+    a = __builtin_fmaf(o.c1, d, a);
+    const float gg = g * g;
+    const float bb = b * o.beta2;
+    b = __builtin_fmaf(o.c2, gg, bb);
+    const float s = sqrtf(b) / bc2s;
+    const float den = s + o.eps;
+    const float q = a / den;
+    w = __builtin_fmaf(-step_size, q, w);
+  } else if (o.kind == DCTR_LAZY_RMSPROP) {
+    const float gg = g * g;
+    const float aa = a * o.beta2;
+    a = __builtin_fmaf(o.beta1, gg, aa);
+    const float den = sqrtf(a) + o.eps;
+    const float q = g / den;
+    w = __builtin_fmaf(-o.lr, q, w);
+  } else if (o.kind == DCTR_LAZY_ADAGRAD) {     // (torch.optim.Adagrad's foreach step: addcmul, sqrt, add, addcdiv)
+    const float gg = g * g;
+    a = __builtin_fmaf(1.f, gg, a);
+    const float den = sqrtf(a) + o.eps;
+    const float q = g / den;
+    w = __builtin_fmaf(-o.lr, q, w);
+  } else {
+    w = __builtin_fmaf(-o.lr, g, w);
+  }
+}
+template <bool FAST = false, bool PIN = false>
 __device__ __forceinline__ void opt_step(const OptConst& o, float g, float& w, float& a, float& b, float step_size,
                                          float bc2s, float rbc = 0.f) {
   if (o.kind == DCTR_LAZY_ADAM && FAST && !DCTR_LAZY_REPLAY_NR) {
-    adam_replay_step<float>(1.f - o.beta1, 1.f - o.beta2, o.beta2, o.eps, g, step_size, rbc, w, a, b);
+    adam_replay_step<float>(o.c1, o.c2, o.beta2, o.eps, g, step_size, rbc, w, a, b);
+  } else if (PIN) {
+    opt_step_pinned(o, g, w, a, b, step_size, bc2s);
   } else if (o.kind == DCTR_LAZY_ADAM) {
-    a = a + (g - a) * (1.f - o.beta1);
-    b = b * o.beta2 + (1.f - o.beta2) * g * g;
+    a = a + (g - a) * o.c1;
+    b = b * o.beta2 + o.c2 * g * g;
     if (FAST) {
       const float denom = div_nr(sqrt_nr(b), bc2s, rbc) + o.eps;
       w = w - step_size * div_nr(a, denom, __builtin_amdgcn_rcpf(denom));
@@ -191,6 +242,8 @@ __device__ __forceinline__ void opt_step(const OptConst& o, float g, float& w, f
 inline OptConst opt_const(const dctr_lazy_opt_t* opt) {
   OptConst o;
   o.kind = opt->kind; o.lr = opt->lr; o.eps = opt->eps; o.beta1 = opt->beta1; o.beta2 = opt->beta2;
+  o.c1 = opt->beta1_c != 0.f ? opt->beta1_c : 1.f - opt->beta1;
+  o.c2 = opt->beta2_c != 0.f ? opt->beta2_c : 1.f - opt->beta2;
   const bool tab = opt->kind == DCTR_LAZY_ADAM && opt->adam_ss && opt->adam_bc && opt->n_ss > 0 && opt->n_bc > 0;
   o.adam_ss = tab ? opt->adam_ss : nullptr;
   o.adam_bc = tab ? opt->adam_bc : nullptr;

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdctr_hip.so")
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
 
@@ -91,6 +91,12 @@ class DenseItem(ctypes.Structure):
                 ("l2", ctypes.c_float), ("pad_", ctypes.c_float)]
 
 
+class DenseItem2(ctypes.Structure):
+    """``dctr_dense_item2_t`` (include/dctr.h): one tensor of a ``dctr_dense_opt_multi_reg`` list."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("s1", ctypes.c_void_p), ("s2", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("l2", ctypes.c_float), ("pad_", ctypes.c_float)]
+
+
 GATE_MAX_GATES, GATE_MAX_MEMBERS, GATE_MAX_POOL, GATE_MAX_WIDTH = 8, 16, 32, 1152
 
 
@@ -132,7 +138,8 @@ class LazyOpt(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("lr", ctypes.c_float), ("eps", ctypes.c_float),
                 ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
                 ("n_ss", ctypes.c_int32), ("n_bc", ctypes.c_int32), ("any_l2", ctypes.c_int32),
-                ("adam_ss", ctypes.c_void_p), ("adam_bc", ctypes.c_void_p), ("adam_rbc", ctypes.c_void_p)]
+                ("adam_ss", ctypes.c_void_p), ("adam_bc", ctypes.c_void_p), ("adam_rbc", ctypes.c_void_p),
+                ("beta1_c", ctypes.c_float), ("beta2_c", ctypes.c_float)]
 POOL_CODE = {None: 0, "sum": 1, "mean": 2, "max": 3}
 BWD_ACCUM, BWD_SGD = 0, 1
 OPT_SGD, OPT_ADAGRAD = 0, 1
@@ -243,6 +250,8 @@ SIGNATURES = {
     "dctr_sizeof_dense_item": (ctypes.c_size_t, []),
     "dctr_dense_opt_multi": (ctypes.c_int, [ctypes.POINTER(DenseItem), _I32, _I32, _F32, _F32, _P]),
     "dctr_l2_value_multi": (ctypes.c_int, [ctypes.POINTER(DenseItem), _I32, _P, _P]),
+    "dctr_sizeof_dense_item2": (ctypes.c_size_t, []),
+    "dctr_dense_opt_multi_reg": (ctypes.c_int, [ctypes.POINTER(DenseItem2), _I32, _P, _P, _P]),
     "dctr_shard_assemble_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I64, _P, _I32, _I32, _P, _P,
                                                _I32, _P, _I64, _P, _P, _P, _I64, _P]),
     "dctr_shard_assemble_bwd": (ctypes.c_int, [_P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I64, _P, _P, _P, _I64, _P,
@@ -353,6 +362,7 @@ def lib():
                 or handle.dctr_sizeof_lazy_opt() != ctypes.sizeof(LazyOpt) \
                 or handle.dctr_sizeof_dense_step() != ctypes.sizeof(DenseStep) \
                 or handle.dctr_sizeof_dense_item() != ctypes.sizeof(DenseItem) \
+                or handle.dctr_sizeof_dense_item2() != ctypes.sizeof(DenseItem2) \
                 or handle.dctr_sizeof_gate() != ctypes.sizeof(Gate) \
                 or handle.dctr_sizeof_mlr() != ctypes.sizeof(Mlr):
             raise RuntimeError("dctr_field_t / dctr_plan_t / dctr_mlp_t layout mismatch between header and binding")

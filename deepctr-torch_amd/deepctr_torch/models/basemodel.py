@@ -159,6 +159,9 @@ class BaseModel(nn.Module):
         self._flush_lazy()       # the pickled tables are the reference's tables
         d = dict(self.__dict__)
         d["_fit_graph"] = None
+        d.pop("_dense_clock", None)       # (ctypes descriptors, a device counter, the library handle: rebuilt on demand --
+        d.pop("_multi_reg_probe", None)   # the count was just written back to the optimizer's state)
+        d.pop("_stacked_pending", None)
         if d.get("_fused"):       # the step engine holds ctypes descriptors and device buffers: rebuilt on demand
             d["_fused"] = {k: v for k, v in d["_fused"].items() if k != "engine"}
         return d
@@ -173,6 +176,7 @@ class BaseModel(nn.Module):
         if fused and fused.get("slab") is not None and not (
                 fused["slab"].flat.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             fused["slab"].sync_optimizer_state()      # Adam's per-parameter `step` entries
+        self._dense_clock_sync()                      # ... and those of the autograd step's dense parameters
 
     def state_dict(self, *args, **kwargs):
         """The reference's keys / shapes / values -- as COPIES for every entry that is a view of a larger storage (all
@@ -629,6 +633,156 @@ class BaseModel(nn.Module):
         m = match_optimizer(getattr(self, "optim", None), params)
         return m if m is not None and m[0] != "rmsprop" else None
 
+    # ------------------------------------------------------------------------------------------------
+    # Adam / RMSprop on the autograd route: the multi-tensor kernel with a device-side step count
+    # ------------------------------------------------------------------------------------------------
+    def _multi_adam_ok(self):
+        """True when the Adam / RMSprop step of the autograd route may run on ``dctr_dense_opt_multi_reg``: not switched
+        off (DCTR_MULTI_ADAM=0 / DCTR_MULTI_STEP=0) and the loaded library has the entry point (probed once per library
+        object; one without it leaves these optimizers on ``optim.step()``)."""
+        if os.environ.get("DCTR_MULTI_ADAM", "1") == "0" or os.environ.get("DCTR_MULTI_STEP", "1") == "0":
+            return False
+        from .._hip import lib as L
+        try:
+            handle = L.lib()
+        except Exception:
+            return False
+        probe = self.__dict__.get("_multi_reg_probe")
+        if probe is None or probe[0] is not handle:
+            probe = self._multi_reg_probe = (handle, hasattr(handle, "dctr_dense_opt_multi_reg") and
+                                             hasattr(handle, "dctr_lazy_step_inc"))
+        return probe[1]
+
+    def _multi_update_mode(self, params):
+        """``match_optimizer`` for the multi-tensor route: like ``_dense_update_mode``, plus ``("rmsprop", lr, eps, alpha)``;
+        Adam / RMSprop only while ``_multi_adam_ok()``."""
+        m = match_optimizer(getattr(self, "optim", None), params)
+        if m is not None and m[0] in ("adam", "rmsprop") and not self._multi_adam_ok():
+            return None
+        return m
+
+    _MOMENTS = {"adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}
+
+    @staticmethod
+    def _capturing(device):
+        return torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def _moments_of(self, params, mode):
+        """The optimizer's own state tensors of ``params`` for the kernel (created as zeros, with ``step``, where torch has
+        not yet: torch does so at its first ``step()``), or None when one of them is not a plain fp32 tensor laid out like
+        its parameter."""
+        out = []
+        for p in params:
+            st = self.optim.state[p]
+            row = []
+            for key in self._MOMENTS[mode[0]]:
+                if key not in st:
+                    if self._capturing(p.device):
+                        raise RuntimeError("optimizer state would be created inside a graph capture")
+                    st.setdefault("step", torch.tensor(0.0, dtype=torch.float32))
+                    st[key] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+                s = st[key]
+                if not torch.is_tensor(s) or s.dtype != torch.float32 or not s.is_contiguous() or \
+                        s.device != p.device or s.shape != p.shape:
+                    return None
+                row.append(s)
+            out.append(row)
+        return out
+
+    def _dense_clock_sync(self, release=False):
+        """The per-parameter ``state["step"]`` entries (torch's host-side count) of the parameters the kernel steps follow
+        the device counter; ``release``: the counter also gives the parameters up (torch is about to step them itself: it
+        is adopted again from their entries afterwards).  Never inside a capture: the counter cannot be read there."""
+        ck = self.__dict__.get("_dense_clock")
+        if ck is None or not ck["members"]:
+            return
+        if self._capturing(ck["step"].device):
+            if release:
+                raise RuntimeError("the dense step count cannot be handed back to torch inside a graph capture")
+            return
+        t = float(int(ck["step"].item()))
+        for p in ck["members"].values():
+            st = ck["optim"].state.get(p)
+            if st is not None and "step" in st:
+                st["step"] = torch.tensor(t, dtype=st["step"].dtype) if torch.is_tensor(st["step"]) else t
+        if release:
+            ck["members"] = {}
+            ck["full"] = 0
+
+    def _dense_clock_claim(self, params, mode):
+        """The device-side step counter of the dense parameters (an int32 tensor, one per optimizer object, the ``step``
+        argument of ``dctr_dense_opt_multi_reg`` / ``dctr_dense_opt_reg``) set up for stepping exactly ``params`` -- or
+        None when it cannot speak for them: it is adopted from their host ``state["step"]`` entries, which must agree.  When
+        the SET of parameters differs from the previous step's (a gradient that is None this time), the count is first
+        written back to the old set.  Nothing of this can happen inside a capture: raises there."""
+        dev = params[0].device
+        ck = self.__dict__.get("_dense_clock")
+        if ck is not None and (ck["optim"] is not self.optim or ck["step"].device != dev):
+            self._dense_clock_sync(release=True)
+            ck = None
+        if ck is None:
+            if self._capturing(dev):
+                raise RuntimeError("the dense step counter would be created inside a graph capture")
+            ck = self._dense_clock = {"optim": self.optim, "step": torch.zeros((1,), dtype=torch.int32, device=dev),
+                                      "members": {}, "mode": None, "opt": None, "tabs": None, "full": 0}
+            opt = self.optim
+            if not getattr(opt, "_dctr_clock_hooks", False):
+                import weakref
+                ref = weakref.ref(self)
+
+                def before_state_dict(optimizer):
+                    model = ref()
+                    ck2 = model.__dict__.get("_dense_clock") if model is not None else None
+                    if ck2 is not None and ck2["optim"] is optimizer:
+                        model._dense_clock_sync()
+
+                def after_load(optimizer):       # the loaded entries are the truth: adopt from them at the next step
+                    model = ref()
+                    ck2 = model.__dict__.get("_dense_clock") if model is not None else None
+                    if ck2 is not None and ck2["optim"] is optimizer:
+                        ck2["members"] = {}
+                        ck2["full"] = 0
+                if hasattr(opt, "register_state_dict_pre_hook"):
+                    opt.register_state_dict_pre_hook(before_state_dict)
+                if hasattr(opt, "register_load_state_dict_post_hook"):
+                    opt.register_load_state_dict_post_hook(after_load)
+                opt._dctr_clock_hooks = True
+        if ck["mode"] != mode:
+            if self._capturing(dev):
+                raise RuntimeError("the optimizer's hyper-parameters changed inside a graph capture")
+            from .._hip import lib as L
+            from .._hip.plan import LazyState
+            o = L.LazyOpt()
+            tabs = None
+            if mode[0] == "adam":
+                o.kind, o.lr, o.eps, o.beta1, o.beta2 = L.LAZY_ADAM, mode[1], mode[2], mode[3], mode[4]
+                o.beta1_c, o.beta2_c = 1 - mode[3], 1 - mode[4]       # (rounded from double, like torch's scalars)
+                # Adam's step-dependent scalars as torch computes them on the host (in double, from the hyper-parameters
+                # as the optimizer holds them), tabulated by step number -- the tables of the lazily updated tables
+                t = LazyState.adam_tables(mode[1], mode[3], mode[4], LazyState.ADAM_TABLE_MAX)
+                if t is not None:
+                    tabs = tuple(torch.from_numpy(a).to(dev) for a in t[:2])
+                    o.adam_ss, o.n_ss = tabs[0].data_ptr(), tabs[0].numel()
+                    o.adam_bc, o.n_bc = tabs[1].data_ptr(), tabs[1].numel()
+            else:       # (beta1 carries 1 - alpha, rounded from double like the scalar torch hands its kernels)
+                o.kind, o.lr, o.eps, o.beta1, o.beta2 = L.LAZY_RMSPROP, mode[1], mode[2], 1 - mode[3], mode[3]
+            ck["mode"], ck["opt"], ck["tabs"] = mode, o, tabs
+        members = ck["members"]
+        if len(members) == len(params) and all(id(p) in members for p in params):
+            return ck
+        if self._capturing(dev):
+            raise RuntimeError("the set of dense parameters with a gradient changed inside a graph capture")
+        self._dense_clock_sync(release=True)
+        counts = set()
+        for p in params:
+            st = self.optim.state.get(p, {})
+            counts.add(int(float(st["step"])) if "step" in st else 0)
+        if len(counts) != 1:
+            return None
+        ck["step"].fill_(counts.pop())
+        ck["members"] = dict((id(p), p) for p in params)
+        return ck
+
     def _fused_step_state(self):
         """The fused train step applies when every piece of the step is one of our kernels: binary task with
         BCE(sum), no regulariser / auxiliary loss, tables on the fused sparse update, and every dense parameter
@@ -807,14 +961,14 @@ class BaseModel(nn.Module):
     def _fusable_l2(self):
         """``{id(p): (p, lambda)}`` when every regularisation term of the model is a plain L2 term on a dense parameter
         that ``_step_dense_multi`` is certain to step (one term per parameter; fp32, contiguous, on the GPU; the whole
-        optimizer a plain SGD / Adagrad with one lr): the kernel then adds ``2 lambda p`` to the gradient itself -- for
+        optimizer a plain SGD / Adagrad / Adam / RMSprop with one lr): the kernel then adds ``2 lambda p`` to the gradient itself -- for
         DCN's default ``l2_reg_cross`` the autograd route is ~40 launches of pow / mul / sum / add per step.  ``None``
         when anything else is regularised (L1, a table on the dense-gradient route, a stacked weight group, ...)."""
         if os.environ.get("DCTR_MULTI_STEP", "1") == "0" or os.environ.get("DCTR_FUSED_L2", "1") == "0":
             return None
         every = [p for grp in self.optim.param_groups for p in grp["params"]]
-        mode = self._dense_update_mode(every)
-        if mode is None or mode[0] not in ("sgd", "adagrad"):
+        mode = self._multi_update_mode(every)       # (Adam / RMSprop: only while the kernel route takes them)
+        if mode is None:
             return None
         lazy_ids = set()
         if self._plan is not None and self._plan.update[0] == "lazy":
@@ -869,11 +1023,15 @@ class BaseModel(nn.Module):
         ``2 lambda p``); parameters it cannot take (non-contiguous, another dtype / device) are left to ``optim.step()``
         with the stepped ones hidden.  Skipping ``optim.step()`` keeps its bookkeeping honest by hand: Adagrad's per-parameter
         ``state['step']`` and the ``_step_count`` that learning-rate schedulers check are advanced here."""
+        stacked = self.__dict__.pop("_stacked_pending", None) or []
         if os.environ.get("DCTR_MULTI_STEP", "1") == "0":
             return False, None
+        held = set(id(w) for (ws, _, _, _) in stacked for w in ws)
         todo, rest = [], []
         for grp in self.optim.param_groups:
             for p in grp["params"]:
+                if id(p) in held:
+                    continue
                 g = p.grad
                 if g is None and l2map and id(p) in l2map:
                     g = p.grad = torch.zeros_like(p)      # (autograd would have left 2 lambda p here)
@@ -886,13 +1044,17 @@ class BaseModel(nn.Module):
                     rest.append(p)
         if l2map and any(id(p) in l2map for p in rest):
             raise RuntimeError("an L2-regularised parameter changed its layout during the step")
-        if not todo:
+        if not todo and not stacked:
+            self._dense_clock_sync(release=True)        # (whatever torch steps now, it steps by its own count)
             return False, None
-        mode = self._dense_update_mode(todo)
-        if mode is None or mode[0] not in ("sgd", "adagrad"):
+        mode = self._multi_update_mode(todo + [w for (ws, _, _, _) in stacked for w in ws])
+        if mode is None:
             if l2map:
                 raise RuntimeError("the optimizer changed under a train step with fused L2 terms")
+            self._dense_clock_sync(release=True)
             return False, None
+        if mode[0] in ("adam", "rmsprop"):
+            return self._step_dense_multi_reg(todo, rest, stacked, mode, l2map)
         import ctypes
         from .._hip import lib as L
         if mode[0] == "adagrad":
@@ -935,13 +1097,110 @@ class BaseModel(nn.Module):
         self.optim._opt_called = True         # (... and what newer ones check)
         return True, reg
 
+    def _step_dense_multi_reg(self, todo, rest, stacked, mode, l2map):
+        """``_step_dense_multi`` under a plain Adam / RMSprop: the stacked groups ``_step_stacked_groups`` left pending (one
+        ``dctr_dense_opt_reg`` launch each), then ``dctr_dense_opt_multi_reg`` over ``todo`` (one launch per 48 tensors), all
+        reading step number ``*counter + 1`` from the device, then ONE ``dctr_lazy_step_inc``.  Nothing in these launches
+        changes from step to step on the host: the step replays from a hipGraph.  The state tensors torch sees
+        (``exp_avg``, ``exp_avg_sq`` / ``square_avg``) ARE the kernel's state; torch's per-parameter ``state["step"]``
+        follows the device counter whenever somebody is about to look (``_dense_clock_sync``)."""
+        import ctypes
+        from .._hip import lib as L
+        moments = self._moments_of(todo, mode)
+        ck = None
+        if moments is not None:
+            ck = self._dense_clock_claim(todo + [w for (ws, _, _, _) in stacked for w in ws], mode)
+        if ck is None:
+            # this step is torch's (step counts that disagree, state in another layout).  The fused L2 terms are not in the
+            # autograd graph: add what autograd would have left in .grad, and their value for the logged loss
+            self._dense_clock_sync(release=True)
+            reg = None
+            if l2map:
+                with torch.no_grad():
+                    for p, lam in l2map.values():
+                        v = lam * torch.sum(torch.square(p))
+                        reg = v if reg is None else reg + v
+                        p.grad.add_(p, alpha=2.0 * lam)
+                    reg = reg.reshape(1)
+            return False, reg
+        lib = L.lib()
+        dev = ck["step"].device
+        stream = L.stream_handle(dev)
+        counter, opt = ctypes.c_void_p(ck["step"].data_ptr()), ctypes.byref(ck["opt"])
+        P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+        for ws, slab, g0, sts in stacked:
+            L.check(lib.dctr_dense_opt_reg(P(slab), P(g0), P(sts[0]), P(sts[1]) if len(sts) > 1 else None, None,
+                                           slab.numel(), opt, counter, stream), "dctr_dense_opt_reg(stacked group)")
+            for w in ws:
+                w.grad = None
+        reg = None
+        if todo:
+            items = (L.DenseItem2 * len(todo))()
+            for i, p in enumerate(todo):
+                items[i].p, items[i].g, items[i].n = p.data_ptr(), p.grad.data_ptr(), p.numel()
+                items[i].s1 = moments[i][0].data_ptr()
+                items[i].s2 = moments[i][1].data_ptr() if len(moments[i]) > 1 else None
+                items[i].l2 = l2map[id(p)][1] if (l2map and id(p) in l2map) else 0.0
+            if l2map:
+                # value of the fused terms on the weights the forward used (before the step), for the logged loss
+                terms = list(l2map.values())          # (every one of them is in `todo`: checked above)
+                old = (L.DenseItem * len(terms))()
+                for i, (p, lam) in enumerate(terms):
+                    old[i].p, old[i].g, old[i].state, old[i].n, old[i].l2 = p.data_ptr(), None, None, p.numel(), lam
+                reg = torch.empty((1,), dtype=torch.float32, device=dev)
+                L.check(lib.dctr_l2_value_multi(old, len(terms), ctypes.c_void_p(reg.data_ptr()), stream),
+                        "dctr_l2_value_multi")
+            L.check(lib.dctr_dense_opt_multi_reg(items, len(todo), opt, counter, stream), "dctr_dense_opt_multi_reg")
+        L.check(lib.dctr_lazy_step_inc(counter, stream), "dctr_lazy_step_inc")
+        if rest:
+            for p in todo:
+                p.grad = None
+            ck["full"] = 0
+            self._dense_clock_sync()          # torch steps `rest` by its own count; the stepped ones show theirs
+            return False, reg
+        ck["full"] += 1
+        if hasattr(self.optim, "_step_count"):
+            self.optim._step_count += 1
+        self.optim._opt_called = True
+        return True, reg
+
+    def _stacked_moments(self, tag, ws, slab, mode, states):
+        """Adam's / RMSprop's state of a stacked weight group as slices of one state slab per moment (re-seated once, like
+        Adagrad's ``sum``; created as zeros where torch has not yet)."""
+        out = []
+        for key in self._MOMENTS[mode[0]]:
+            st = states.get((tag, key))
+            cur = self.optim.state[ws[0]].get(key)
+            if st is None or st.shape != slab.shape or st.device != slab.device or cur is None or \
+                    cur.data_ptr() != st.data_ptr():
+                if self._capturing(slab.device):
+                    raise RuntimeError("optimizer state would be re-seated inside a graph capture")
+                parts = []
+                for w in ws:
+                    s = self.optim.state[w]
+                    if key not in s:
+                        s.setdefault("step", torch.tensor(0.0, dtype=torch.float32))
+                        s[key] = torch.zeros_like(w.data, memory_format=torch.contiguous_format)
+                    parts.append(s[key])
+                st = torch.stack(parts).contiguous()
+                if st.shape != slab.shape or st.dtype != torch.float32:
+                    return None
+                for i, w in enumerate(ws):
+                    self.optim.state[w][key] = st[i]
+                states[(tag, key)] = st
+            out.append(st)
+        return out
+
     def _step_stacked_groups(self):
         """Layers that keep many small parameters as slices of one slab (FiBiNET's 2 x 325 bilinear ``nn.Linear``
         weights, whose gradients the kernels write as one ``[n_w, D, D]`` tensor as well) are stepped with ONE
         ``dctr_dense_opt`` launch per group here -- ``torch.optim``'s foreach kernels over 655 tensors were 30 launches,
         161 us per FiBiNET step -- and then hidden from ``optim.step()`` (gradient None: torch skips them).  Only for a
         plain SGD / Adagrad over the group (the same condition as the fused dense step); the optimizer's ``sum`` state
-        of the group is re-seated once as slices of a state slab, so ``optimizer.state_dict()`` keeps working."""
+        of the group is re-seated once as slices of a state slab, so ``optimizer.state_dict()`` keeps working.  Under a
+        plain Adam / RMSprop (``_multi_update_mode``) the group's ``exp_avg`` / ``exp_avg_sq`` / ``square_avg`` are re-seated
+        likewise and the launch is left to ``_step_dense_multi``, which every caller runs next (``_stacked_pending``)."""
+        self.__dict__.pop("_stacked_pending", None)
         if os.environ.get("DCTR_STACKED_STEP", "1") == "0":
             return
         groups = self.__dict__.get("_stacked_cache")
@@ -965,14 +1224,23 @@ class BaseModel(nn.Module):
             g0 = ws[0].grad
             if g0 is None or not slab.is_cuda:
                 continue
-            mode = self._dense_update_mode(ws)
-            if mode is None or mode[0] not in ("sgd", "adagrad"):
+            mode = self._multi_update_mode(ws)
+            if mode is None:
                 continue
             n, step = slab.numel(), slab[0].numel() * 4
             gl = ws[-1].grad
             if gl is None or g0.dtype != torch.float32 or not g0.is_contiguous() or \
                     gl.data_ptr() != g0.data_ptr() + (len(ws) - 1) * step:
                 continue          # the gradients are not the kernels' single [n_w, D, D] tensor: leave it to torch
+            if mode[0] in ("adam", "rmsprop"):
+                # one dctr_dense_opt_reg launch per group on the slab, enqueued by _step_dense_multi (which follows): the
+                # step number is the device counter it shares with the other dense parameters
+                if slab.dtype != torch.float32 or not slab.is_contiguous():
+                    continue
+                sts = self._stacked_moments(id(mod), ws, slab, mode, states)
+                if sts is not None:
+                    self.__dict__.setdefault("_stacked_pending", []).append((ws, slab, g0, sts))
+                continue
             st = None
             if mode[0] == "adagrad":
                 st = states.get(id(mod))
@@ -1008,6 +1276,14 @@ class BaseModel(nn.Module):
             return True
         if type(opt) is torch.optim.Adagrad:
             return all(g.get("lr_decay", 0) == 0 for g in opt.param_groups)
+        if type(opt) in (torch.optim.Adam, torch.optim.RMSprop):
+            # plain Adam / RMSprop on dctr_dense_opt_multi_reg: the step count is read from the device.  Only once the
+            # kernel stepped EVERY parameter with a gradient in the (two) warm-up steps -- their state exists, the
+            # counter is adopted, nothing is left to optim.step()
+            ck = self.__dict__.get("_dense_clock")
+            every = [p for grp in opt.param_groups for p in grp["params"]]
+            return ck is not None and ck["optim"] is opt and ck["full"] >= 2 and self._multi_adam_ok() and \
+                self._multi_update_mode(every) == ck["mode"]
         return False
 
     def _fit_group_size(self, n_full, on_gpu):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DCTR_ABI_VERSION 34
+#define DCTR_ABI_VERSION 35
 
 #define DCTR_OK 0
 #define DCTR_EINVAL (-1) /* null / negative / inconsistent argument            */
@@ -719,6 +719,10 @@ typedef struct dctr_lazy_opt {
   const float* adam_rbc; /* optional (ABI 24), n_bc entries: (float)(1 / sqrt(1 - beta2^T)) -- the replay loop divides by
                             adam_bc[T - 1] through this reciprocal; NULL: it takes the hardware reciprocal of adam_bc itself,
                             one quarter-rate instruction per replayed step and wavefront */
+  float beta1_c, beta2_c; /* optional (ABI 35), Adam: (float)(1 - beta1), (float)(1 - beta2) rounded from DOUBLE, the scalars
+                             torch.optim.Adam hands its kernels (lerp weight, addcmul value).  0: the kernels use
+                             1.f - beta1 / 1.f - beta2 as before -- float(0.999) is 1.3e-8 off 0.999, so that 1.f - beta2 is
+                             1.3e-5 (relative) off 0.001: the same in every increment of exp_avg_sq */
 } dctr_lazy_opt_t;
 size_t dctr_sizeof_lazy_unit(void);
 /* Round 6 -- the step that carries the batch's DATA gradient, inside the sorted update: dctr_embed_update's gradient sums
@@ -1139,6 +1143,28 @@ int dctr_dense_opt_multi(const dctr_dense_item_t* items, int32_t n_items, int32_
 /* out[0] = sum_i l2_i * sum(p_i^2): the value of those terms for the logged loss; one workgroup, fixed summation order.
  * (g / state of the items are not read.)                                                                            */
 int dctr_l2_value_multi(const dctr_dense_item_t* items, int32_t n_items, float* out, dctr_stream_t stream);
+/* ABI 35 -- the multi-tensor step for every kind of dctr_lazy_opt_t (SGD, Adagrad, Adam, RMSprop) with a DEVICE-side step
+ * count: optimizer step number *step + 1 (read, NOT advanced) on a list of contiguous fp32 tensors, one launch per 48
+ * tensors; every launch of a longer list reads the same *step, and the caller advances the counter ONCE afterwards with
+ * dctr_lazy_step_inc.  torch.optim.Adam computes its bias corrections on the host, so its step cannot be replayed from a
+ * hipGraph; this one can.  g + 2*l2*p enters the step where l2 != 0 (rounded like autograd: product, then sum).  The
+ * arithmetic per element is that of dctr_dense_opt_reg / the lazy table update (csrc/lazy_opt.hpp), IEEE division and
+ * square root.  opt->adam_ss / adam_bc (optional, as for the tables): Adam's scalars by step number.
+ *   s1: Adagrad sum | Adam exp_avg | RMSprop square_avg      s2: Adam exp_avg_sq      (ignored where the kind has none)
+ * items: HOST array.  DCTR_EINVAL -- before anything is launched -- on a NULL opt or step, an unknown kind, n < 0, or a
+ * tensor with n > 0 that lacks p, g or a state its kind needs; n_items == 0 or all n == 0: DCTR_OK, nothing launched. */
+typedef struct dctr_dense_item2 {
+  float* p;
+  const float* g;
+  float* s1;
+  float* s2;
+  int64_t n;
+  float l2;
+  float pad_;
+} dctr_dense_item2_t;
+size_t dctr_sizeof_dense_item2(void);
+int dctr_dense_opt_multi_reg(const dctr_dense_item2_t* items, int32_t n_items, const dctr_lazy_opt_t* opt,
+                             const int32_t* step, dctr_stream_t stream);
 
 /* ---- table-sharded multi-GPU exchange: the two "assemble" kernels (csrc/shard.hip, deepctr_torch/parallel.py) ---
  * Rank q of N owns units q, q+N, q+2N, ... (a unit = one id column with its deep and/or wide table).  Owners gather
